@@ -2,6 +2,17 @@
 """bench.py -- SSIMULACRA2 frame-pairs/s on synthetic decoded streams, one process per GPU.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 1080p_nv12|4k_p016] [--batch B] [--metrics ...]
+                  [--full] [--dump-outputs DIR]
+
+A plain run measures the headline only: it sets up, settles and warms up, times the K steps, writes --dump-outputs and prints
+the line (contract fields, the roofline of the timed steps' stage timers, per_rank, stage_ms).  --full adds every other leg
+below: the other full_sums setting (`compare`), the kernels alone on the chip (`kernels_alone` and the roofline's *_alone figures),
+`fixed_stream`, `workloads`, `host_fed`, `batch_curve`, `cli_end_to_end` and `cpu_baseline` (each still subject to its --no-*
+switch).  An explicit --stream-pairs runs the fixed stream in a plain run too.
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed -- the per-pair scores of every requested metric
+(every rank's batch, gathered on rank 0 like the scores of the path: float64, DIR/<metric>.npy) -- so that two builds can be compared output for output; the synthetic inputs are a
+pure function of the arguments.
 
 A "step" is one pass of the hot path (ingest -> XYB pyramid -> column pass -> row pass + error maps +
 reductions -> 108 sums per pair -> scores) over one batch of B frame pairs whose decoded surfaces are
@@ -81,6 +92,9 @@ def parse_args():
     ap.add_argument("--detail-file", default=None, help="where the full record goes (default: bench_detail.json beside bench.py, and a copy "
                     "under gpurun_out/ when that directory exists); the stdout line is the compact one (<= 4 KB)")
     ap.add_argument("--cpu-pairs", type=int, default=0, help="pairs timed for cpu_baseline (0 = auto, ~15 s)")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline (compare, kernels alone, fixed streams, "
+                    "workloads, host-fed, batch curve, CLI, CPU baseline); default: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the per-pair scores of the last timed step as DIR/<metric>.npy (float64)")
     return ap.parse_args()
 
 
@@ -307,9 +321,18 @@ def run_workload(ctx, args, name, mets, B, steps, warmup, settle_ms, compare, ke
         all_scores = tm.shard.reduce_scores(scores_local, ctx.rank * B, ctx.world * B, 1, ctx.dist, rdev)
         torch.cuda.synchronize()
         reduce_ms.append(ctx.max_over_ranks(time.perf_counter() - t_r) * 1e3)
+    outputs = None
+    if args.dump_outputs:
+        # what a caller receives from the last timed step: every metric's scores of every rank's block, on rank 0 (one more reduce,
+        # outside the timing; None on the other ranks)
+        names = sorted(mets)
+        got = tm.shard.reduce_scores(np.array([[getattr(s, m) for m in names] for s in sc], np.float64), ctx.rank * B, ctx.world * B,
+                                     len(names), ctx.dist, rdev)
+        if got is not None:
+            outputs = {m: got[:, i].copy() for i, m in enumerate(names)}
 
     alone = None
-    if has_s2 and eng.uses_fused_edge(B) and args.edge_beside == 1:
+    if args.full and has_s2 and eng.uses_fused_edge(B) and args.edge_beside == 1:
         # the fused kernel of the edge-only jobs runs BESIDE the two blur passes (second stream): the stage times above overlap.
         # A few steps with it BEHIND the row pass instead (outside the headline timing) time every kernel alone on the chip.
         eng.debug_set_edge_beside(0)
@@ -395,13 +418,14 @@ def run_workload(ctx, args, name, mets, B, steps, warmup, settle_ms, compare, ke
     stage_ach = stage_bytes * B / ((ms_v + ms_h + ms_e) * 1e-3) / 1e9 if ms_v + ms_h > 0 else 0.0
     bytes_model = ("SURVEY 8d (84 B/px/pass)" if args.full_sums else
                    "SURVEY 8d restricted to the planes that carry weight (job table)" + ("; the edge-only jobs run in k_blur_edge_fused (algorithmic bytes: their input, read once)" if fused_edge else ""))
-    if alone is not None:
+    if fused_edge and args.edge_beside == 1:
         # The launches that dominate the step run CONCURRENTLY: the fused kernel of the edge-only jobs is a persistent launch beside the
         # column pass and the row pass.  One kernel's bytes over its own duration would leave out what the others move through HBM
         # meanwhile (column pass: its 7.4 GB over 1.9 ms shared = 0.49, over 1.45 ms alone = 0.64) -- the roofline entry is the GROUP:
         # the three kernels' algorithmic bytes over the span from the end of the ingest stage to the end of the row pass, measured
-        # with the HIP events of the timed steps; every member's own figures, beside the others and alone, are listed.
+        # with the HIP events of the timed steps; every member's own figures, beside the others and (--full) alone, are listed.
         grp = ("k_blur_v_jobs", "k_blur_h_jobs_x", "k_blur_edge_fused")
+        own_alone = lambda k: {"avg_launch_ms_alone": alone["kernels"][k]["avg_launch_ms"], "frac_alone": alone["kernels"][k]["frac"]} if alone is not None else {}
         gtraffic = sum(traffic[k] for k in grp) if all(traffic.get(k) for k in grp) else None
         roofline = {"bound": "hbm", "kind": "group", "kernel": "k_blur_v_jobs + k_blur_h_jobs_x + k_blur_edge_fused (one concurrent group)",
                     "achieved": stage_ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": stage_ach / HBM_PEAK_GBS,
@@ -409,8 +433,8 @@ def run_workload(ctx, args, name, mets, B, steps, warmup, settle_ms, compare, ke
                     "algorithmic_bytes_per_launch": stage_bytes * B, "avg_launch_ms": ms_v + ms_h + ms_e, "bytes_model": bytes_model,
                     "members": {k: {"algorithmic_bytes_per_launch": per_kernel[k]["algorithmic_bytes_per_launch"], "traffic": per_kernel[k]["traffic"],
                                     "avg_launch_ms": per_kernel[k]["avg_launch_ms"], "frac": per_kernel[k]["frac"],
-                                    "avg_launch_ms_alone": alone["kernels"][k]["avg_launch_ms"], "frac_alone": alone["kernels"][k]["frac"]} for k in grp},
-                    "longest_hbm_bound_member": dom, "frac_alone": alone["kernels"][dom]["frac"], "avg_launch_ms_alone": alone["kernels"][dom]["avg_launch_ms"],
+                                    **own_alone(k)} for k in grp},
+                    "longest_hbm_bound_member": dom, **own_alone(dom),
                     "region_frac": stage_ach / HBM_PEAK_GBS, "region_ms": ms_v + ms_h + ms_e}
     else:
         roofline = {"bound": "hbm", "kind": "kernel", "kernel": dom, "achieved": per_kernel[dom]["achieved_GBs"], "peak": HBM_PEAK_GBS,
@@ -460,9 +484,9 @@ def run_workload(ctx, args, name, mets, B, steps, warmup, settle_ms, compare, ke
         other["blur_reduce_stage_frac"] = ob * B / ((mv + mh + me) * 1e-3) / 1e9 / HBM_PEAK_GBS if mv + mh > 0 else 0.0
         res["compare"] = other
     if keep_engine:
-        return res, eng, distinct
+        return res, eng, distinct, outputs
     eng.close()
-    return res, None, distinct
+    return res, None, distinct, outputs
 
 
 def run_fixed_stream(ctx, eng, name, B, distinct, total):
@@ -911,6 +935,14 @@ def write_detail(d, path=None):
     return written
 
 
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: one float64 array per metric, the scores a caller of the timed path receives (B values each)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float64))
+
+
 def run_rank(args):
     ctx = Ctx(args)
     head_name = args.workload or "1080p_nv12"
@@ -919,11 +951,13 @@ def run_rank(args):
     # the other workloads, the host-fed leg, the batch curve and the CLI describe ONE GPU: with several ranks the line carries the weak
     # leg (`value`) and the strong leg (`fixed_stream`) only -- eight ranks generating 4K frames on a shared CPU quota is setup time that
     # measures nothing
-    extras = args.workload is None and not args.no_extras and mets == {"ssimulacra2"} and ctx.world == 1
-    res, eng, distinct = run_workload(ctx, args, head_name, mets, B, args.steps, args.warmup, args.settle_ms,
-                                      compare=not args.no_compare, keep_engine=True)
+    extras = args.full and args.workload is None and not args.no_extras and mets == {"ssimulacra2"} and ctx.world == 1
+    res, eng, distinct, outputs = run_workload(ctx, args, head_name, mets, B, args.steps, args.warmup, args.settle_ms,
+                                               compare=args.full and not args.no_compare, keep_engine=True)
+    if outputs is not None:
+        dump_outputs(outputs, args.dump_outputs)
     fixed = None
-    if "ssimulacra2" in mets and (not args.no_extras or args.stream_pairs is not None):
+    if "ssimulacra2" in mets and ((args.full and not args.no_extras) or args.stream_pairs is not None):
         eng.set_full_sums(args.full_sums)
         fixed = run_fixed_stream(ctx, eng, head_name, B, distinct, args.stream_pairs or STREAM_PAIRS)
         if args.stream_pairs is None:  # the default line: a second, longer stream (>= 0.15 s of kernels per rank at 8 GPUs)
@@ -1007,7 +1041,7 @@ def run_rank(args):
             out["batch_curve"] = batch_curve
         if cli:
             out["cli_end_to_end"] = cli
-        if ctx.world == 1 and not args.no_cpu_baseline:
+        if ctx.world == 1 and args.full and not args.no_cpu_baseline:
             w, h, kind = WORKLOADS[head_name][:3]
             out["cpu_baseline"] = cpu_baseline(ctx.tm, w, h, kind, args.cpu_pairs)
         out["detail_file"] = args.detail_file or "bench_detail.json"

@@ -43,9 +43,10 @@ def _bench(extra, env_extra=None):
     return _run(extra, COMMON, env_extra)
 
 
-def test_two_ranks_are_really_started_and_reproduce_the_one_rank_scores():
-    one = _bench(["--gpus", "1"])
-    two = _bench(["--gpus", "2"], {"TM_BENCH_BACKEND": "gloo"})
+def test_two_ranks_are_really_started_and_reproduce_the_one_rank_scores(tmp_path):
+    import numpy as np
+    one = _bench(["--gpus", "1", "--dump-outputs", str(tmp_path / "one")])
+    two = _bench(["--gpus", "2", "--dump-outputs", str(tmp_path / "two")], {"TM_BENCH_BACKEND": "gloo"})
     assert one["n_gpus"] == 1 and one["ranks_seen"] == 1
     assert two["n_gpus"] == 2 and two["ranks_seen"] == 2 and two["fixed_stream"]["ranks_seen"] == 2
     assert two["scaling"] == "weak" and two["fixed_stream"]["scaling"] == "strong"
@@ -57,6 +58,9 @@ def test_two_ranks_are_really_started_and_reproduce_the_one_rank_scores():
     assert one["fixed_stream"]["scores_sha256_16"] == two["fixed_stream"]["scores_sha256_16"]
     for k in ("roofline", "kernels", "stages"):
         assert k in two
+    # --dump-outputs: rank 0 writes the last timed step's scores of every rank's block (8 distinct pairs cycled: rank 1 repeats rank 0)
+    d1, d2 = (np.load(os.path.join(str(tmp_path), k, "ssimulacra2.npy")) for k in ("one", "two"))
+    assert d1.shape == (8,) and d2.shape == (16,) and np.array_equal(d2, np.tile(d1, 2))
 
 
 def test_eight_ranks_rendezvous_shard_and_reduce_like_one_rank():
@@ -85,7 +89,7 @@ def test_eight_ranks_rendezvous_shard_and_reduce_like_one_rank():
 
 def test_the_drivers_eight_gpu_command_with_default_arguments_on_one_device():
     """the command the driver runs at round end -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node 8
-    --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 --steps 20 --warmup 5`, batch 64, both fixed streams -- rehearsed
+    --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 --steps 20 --warmup 5`, batch 64, with --full: both fixed streams -- rehearsed
     on ONE device (TM_BENCH_BACKEND=gloo: the ranks share device 0, gloo carries the collectives).  Every rank caps its thread
     pools to its share of the CPU quota and binds next to its device before any work; the line names the real backend, shows
     the slowest and the fastest rank and the time of the one reduce; < 600 s, <= 4 KB.  The record goes to gpurun_out/ (copied
@@ -99,7 +103,7 @@ def test_the_drivers_eight_gpu_command_with_default_arguments_on_one_device():
         detail = os.path.join(td, "detail.json")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
                "--master-port", str(tm.launch.free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5",
-               "--detail-file", detail]
+               "--full", "--detail-file", detail]
         t0 = time.time()
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
         wall = time.time() - t0
@@ -125,6 +129,30 @@ def test_the_drivers_eight_gpu_command_with_default_arguments_on_one_device():
             json.dump({"command": " ".join(cmd[1:]).replace(ROOT + "/", ""), "env": {"TM_BENCH_BACKEND": "gloo"}, "wall_s": round(wall, 1),
                        "line_bytes": len(lines[0]), "device_mem_used_GB": full.get("device_mem_used_GB"), "rank_cpu": full["rank_cpu"],
                        "line": line}, f, indent=1)
+
+
+def test_a_plain_run_is_the_headline_only_and_dumps_the_last_steps_scores(tmp_path):
+    """no --full: the timed steps and nothing beside them; --dump-outputs writes the scores of the last timed step, the same from run
+    to run, and slot 0 (synthetic pair 0) equals the CPU oracle's score"""
+    import numpy as np
+    from oracle import oracle as O
+    from tm_pkg import tm
+    args = ["--gpus", "1", "--workload", "1080p_nv12", "--steps", "3", "--warmup", "1", "--settle-ms", "0", "--batch", "4"]
+    runs = []
+    for i in range(2):
+        out = str(tmp_path / f"out{i}")
+        runs.append((_run(args, ["--dump-outputs", out]), np.load(os.path.join(out, "ssimulacra2.npy"))))
+    full, got = runs[0]
+    assert full["steps"] == 3 and full["_line"]["ms_per_step"] > 0
+    for k in ("compare", "kernels_alone", "fixed_stream", "workloads", "host_fed", "batch_curve", "cli_end_to_end", "cpu_baseline"):
+        assert k not in full, k
+    assert got.dtype == np.float64 and got.shape == (4,)
+    assert np.array_equal(got, runs[1][1])
+    assert abs(full["score_mean"] - float(np.mean(got))) < 1e-12
+    (rs, rp, rch), (ds, dp, dch) = tm.synth.nv12_pair(1920, 1080, 0)
+    want, _ = O.ssimulacra2_from_linear(O.yuv420_biplanar_to_linear(rs, rp, rch, 1920, 1080, 8, 0),
+                                        O.yuv420_biplanar_to_linear(ds, dp, dch, 1920, 1080, 8, 0))
+    assert abs(got[0] - want) < 1e-6, (got[0], want)
 
 
 def test_asking_for_more_gpus_than_exist_fails_loudly():

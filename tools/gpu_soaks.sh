@@ -1,9 +1,9 @@
 #!/bin/bash
-# GPU box: the long runs of the soak programs (tests/soak/) on the current tree -> gpurun_out/<TAG>_long_soaks.log
+# GPU box: the long runs of the soak programs (tests/soak/) on the current tree -> $OUT/<TAG>_long_soaks.log
 set -u
 TAG=${1:-r06s}
-mkdir -p gpurun_out
-L=gpurun_out/${TAG}_long_soaks.log
+OUT=$(mkdir -p "${OUT:-results}" && cd "${OUT:-results}" && pwd)  # where the outputs go (default results/; absolute: some steps run from /tmp)
+L=$OUT/${TAG}_long_soaks.log
 : > $L
 run() { timeout "$1" python "${@:2}" 2>&1 | grep -v amdgpu.ids | tail -4 >> $L; }
 run 900 tests/soak/variant_sweep_soak.py 5000 1300

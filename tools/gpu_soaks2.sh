@@ -2,8 +2,8 @@
 # GPU box: the soak programs tools/gpu_soaks.sh does not run (threads, SSIM twin, RGB pitches, create / destroy) + further seeds of the random sweep
 set -u
 TAG=${1:-r06v}
-mkdir -p gpurun_out
-L=gpurun_out/${TAG}_more_soaks.log
+OUT=$(mkdir -p "${OUT:-results}" && cd "${OUT:-results}" && pwd)  # where the outputs go (default results/; absolute: some steps run from /tmp)
+L=$OUT/${TAG}_more_soaks.log
 : > $L
 run() { timeout "$1" python "${@:2}" 2>&1 | grep -v amdgpu.ids | tail -3 >> $L; }
 run 600 tests/soak/thread_soak.py 8 200

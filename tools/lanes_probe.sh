@@ -17,5 +17,5 @@ for b in (16, 16, 1, 1, 1, 1):
 print("engine creation ms (batch 16, 16, 1, 1, 1, 1):", t, flush=True)
 PY
 done
-for f in 1; do for q in 1 0; do echo "== TM_BENCH_FORCE_DIST=$f TM_QUEUE_LANES=$q"; RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 TM_QUEUE_LANES=$q TM_BENCH_FORCE_DIST=$f timeout 300 python bench.py --no-extras --no-cpu-baseline --no-compare --steps 40 2>&1 | grep "^{" | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d[\"value\"], d[\"roofline\"][\"frac\"], d[\"summary\"].get(\"stage_ms\"))"; done; done
+for f in 1; do for q in 1 0; do echo "== TM_BENCH_FORCE_DIST=$f TM_QUEUE_LANES=$q"; RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 TM_QUEUE_LANES=$q TM_BENCH_FORCE_DIST=$f timeout 300 python bench.py --full --no-extras --no-cpu-baseline --no-compare --steps 40 2>&1 | grep "^{" | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d[\"value\"], d[\"roofline\"][\"frac\"], d[\"summary\"].get(\"stage_ms\"))"; done; done
 bash tools/cli_ab.sh 1080p 3 "" "TM_QUEUE_LANES=0" "--loop deferred --in-flight 3" "--loop deferred --in-flight 3 TM_QUEUE_LANES=0" "--loop deferred --in-flight 4" "--loop deferred --in-flight 4 TM_QUEUE_LANES=0" 2>&1 | cut -c1-100

@@ -1,17 +1,18 @@
 #!/bin/bash
 # GPU box: SQ-level counters per kernel (one pass, <= 8 SQ counters).  usage: pmc_sq.sh TAG [bench args]
 set -u
+OUT=$(mkdir -p "${OUT:-results}" && cd "${OUT:-results}" && pwd)  # where the outputs go (default results/; absolute: some steps run from /tmp)
 TAG=${1:-sq}
 shift
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$(pwd)
 cd /tmp
-timeout 600 rocprofv3 --pmc ${TM_SQ_COUNTERS:-SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU} --kernel-trace --output-format csv -d $R/gpurun_out/${TAG}_sq -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-compare --no-extras --detail-file /tmp/tm_sq_detail.json "$@" > $R/gpurun_out/${TAG}_sq.log 2>&1
+timeout 600 rocprofv3 --pmc ${TM_SQ_COUNTERS:-SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU} --kernel-trace --output-format csv -d $OUT/${TAG}_sq -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-compare --no-extras --detail-file /tmp/tm_sq_detail.json "$@" > $OUT/${TAG}_sq.log 2>&1
 cd $R
-python3 - <<PY | tee gpurun_out/${TAG}_sq_summary.txt
+python3 - <<PY | tee $OUT/${TAG}_sq_summary.txt
 import csv, glob, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
-for f in glob.glob("gpurun_out/${TAG}_sq/**/*counter_collection.csv", recursive=True):
+for f in glob.glob("$OUT/${TAG}_sq/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         acc[r["Kernel_Name"].split("(")[0][:60]][r["Counter_Name"]].append(float(r["Counter_Value"]))
 for k, d in acc.items():

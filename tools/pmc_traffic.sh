@@ -7,13 +7,13 @@ TAG=${1:-r02}
 WL=${2:-1080p_nv12}
 EXTRA=${3:-}          # e.g. --full-sums
 SUF=${EXTRA:+_full}
-mkdir -p gpurun_out
+OUT=$(mkdir -p "${OUT:-results}" && cd "${OUT:-results}" && pwd)  # where the outputs go (default results/; absolute: some steps run from /tmp)
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
+R=$(pwd)
 cd /tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout 600 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $R/gpurun_out/${TAG}_pmc_${WL}${SUF}_$C -- python3 $R/bench.py --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --no-compare --no-extras $EXTRA > $R/gpurun_out/${TAG}_pmc_$C.log 2>&1
+  timeout 600 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/${TAG}_pmc_${WL}${SUF}_$C -- python3 $R/bench.py --full --workload $WL --steps 3 --warmup 1 --no-cpu-baseline --no-compare --no-extras $EXTRA > $OUT/${TAG}_pmc_$C.log 2>&1
 done
 cd $R
-python3 tools/parse_pmc.py gpurun_out/${TAG}_pmc_${WL}${SUF}_FETCH_SIZE gpurun_out/${TAG}_pmc_${WL}${SUF}_WRITE_SIZE $WL > gpurun_out/${TAG}_pmc_traffic_$WL$SUF.json
-cat gpurun_out/${TAG}_pmc_traffic_$WL$SUF.json
+python3 tools/parse_pmc.py $OUT/${TAG}_pmc_${WL}${SUF}_FETCH_SIZE $OUT/${TAG}_pmc_${WL}${SUF}_WRITE_SIZE $WL > $OUT/${TAG}_pmc_traffic_$WL$SUF.json
+cat $OUT/${TAG}_pmc_traffic_$WL$SUF.json

@@ -747,14 +747,20 @@ VideoFrameSource::VideoFrameSource(std::unique_ptr<Demuxer> demuxer, const Sourc
     // ships 4.4, Debian 11 4.3; 7.0 removed -vsync): the decoder is asked for its version first.  TM_DECODER_ARGS replaces
     // the option altogether (whitespace-separated; may be empty) for decoders that are not ffmpeg.
     const std::vector<std::string> sync_args = decoder_sync_args(decoder_name_);
-    int to_child[2], from_child[2];
-    if (pipe2(to_child, O_CLOEXEC) != 0 || pipe2(from_child, O_CLOEXEC) != 0) vfail(std::string("pipe: ") + strerror(errno));
+    const std::string not_started = std::string(to_string(demuxer_->container())) + "/" + to_string(codec) + " input needs a decoder and `" +
+        decoder_name_ + "` could not be started: MI355X has no video decode engine behind HIP and none is built in; install ffmpeg (or point "
+        "TM_DECODER at a program with its command line), or feed YUV4MPEG2 (`ffmpeg -i in.mkv -f yuv4mpegpipe - | turbo-metrics - ...`)";
+    // exec_status: closed by a successful exec (O_CLOEXEC), or carries the errno of a failed one.  The child's exit status alone cannot
+    // tell: its stdout may reach EOF before the exited child can be reaped.
+    int to_child[2], from_child[2], exec_status[2];
+    if (pipe2(to_child, O_CLOEXEC) != 0 || pipe2(from_child, O_CLOEXEC) != 0 || pipe2(exec_status, O_CLOEXEC) != 0)
+        vfail(std::string("pipe: ") + strerror(errno));
     signal(SIGPIPE, SIG_IGN);
     const pid_t pid = fork();
     if (pid < 0) vfail(std::string("fork: ") + strerror(errno));
     if (pid == 0) {
         dup2(to_child[0], 0); dup2(from_child[1], 1);
-        close(to_child[0]); close(to_child[1]); close(from_child[0]); close(from_child[1]);
+        close(to_child[0]); close(to_child[1]); close(from_child[0]); close(from_child[1]); close(exec_status[0]);
         // one output picture per decoded picture, whatever rate the muxer guesses (raw streams carry no timestamps): without
         // passthrough a constant-frame-rate muxer may duplicate or drop pictures and misalign the reference / distorted pairs
         // (the reference's NVDEC path emits exactly one picture per decode).  dup2 clears O_CLOEXEC on descriptors 0 and 1.
@@ -763,7 +769,19 @@ VideoFrameSource::VideoFrameSource(std::unique_ptr<Demuxer> demuxer, const Sourc
         for (const char *a : {"-f", "yuv4mpegpipe", "-strict", "-1", "pipe:1"}) argv.push_back(a);
         argv.push_back(nullptr);
         execvp(decoder_name_.c_str(), (char *const *)argv.data());
+        const int err = errno;
+        if (write(exec_status[1], &err, sizeof err) < 0) {}
         _exit(127);
+    }
+    close(exec_status[1]);
+    int exec_errno = 0;
+    ssize_t got;
+    while ((got = read(exec_status[0], &exec_errno, sizeof exec_errno)) < 0 && errno == EINTR) {}
+    close(exec_status[0]);
+    if (got == (ssize_t)sizeof exec_errno) {
+        close(to_child[0]); close(to_child[1]); close(from_child[0]); close(from_child[1]);
+        waitpid(pid, nullptr, 0);
+        vfail(not_started);
     }
     child_ = (int)pid;
     close(to_child[0]); close(from_child[1]);
@@ -806,10 +824,7 @@ VideoFrameSource::VideoFrameSource(std::unique_ptr<Demuxer> demuxer, const Sourc
         fclose(out);
         if (feeder_.joinable()) feeder_.join();
         if (child_ > 0) { kill((pid_t)child_, SIGTERM); waitpid((pid_t)child_, nullptr, 0); child_ = -1; }
-        if (missing)
-            vfail(std::string(to_string(demuxer_->container())) + "/" + to_string(codec) + " input needs a decoder and `" + decoder_name_ +
-                  "` could not be started: MI355X has no video decode engine behind HIP and none is built in; install ffmpeg (or point TM_DECODER at a "
-                  "program with its command line), or feed YUV4MPEG2 (`ffmpeg -i in.mkv -f yuv4mpegpipe - | turbo-metrics - ...`)");
+        if (missing) vfail(not_started);
         vfail(std::string("decoder `") + decoder_name_ + "` produced no YUV4MPEG2 stream: " + e.what());
     }
     if (inner_->width() != fmt_.width || inner_->height() != fmt_.height) {
