@@ -25,6 +25,7 @@
 #pragma once
 #include "tm_device_math.h"
 #include "tm_geom.h"
+#include "tm_p10.h"
 #include <type_traits>
 
 // (wave-level sum / shuffle helpers, TM_LDS_BARRIER, TM_WAVES_PER_SIMD, tm_mul24, tm_f4 / tm_g2, DPP lane exchanges: tm_platform.h)
@@ -63,13 +64,7 @@ __device__ __forceinline__ float ld_row(const float *__restrict__ p, int row, in
 // ------------------------------------------------------------------------------------------------
 //   planar     TM_KIND_I420_8 / I420_16: the same conversion; Cb and Cr come from two planes and a 16-bit sample is first
 //              shifted to the top of its 16 bits (a P016 surface holds exactly that)
-// sample x of a TM_KIND_I420_P10 row (tm_geom.h): block x / 384, run (x % 384) / 128, word x % 128
-__device__ __forceinline__ unsigned p10_word_offset(unsigned x) { return ((x / TM_P10_BLOCK) * TM_P10_RUN + (x % TM_P10_RUN)) * 4u; }
-__device__ __forceinline__ unsigned p10_shift(unsigned x) { return 10u * ((x % TM_P10_BLOCK) / TM_P10_RUN); }
-__device__ __forceinline__ unsigned p10_sample(const char *row, unsigned x)
-{
-    return (*(const unsigned *)(row + p10_word_offset(x)) >> p10_shift(x)) & 1023u;
-}
+// sample addressing of a TM_KIND_I420_P10 row: tm_p10.h (p10_word_offset, p10_shift, p10_sample)
 template <typename T, int BITS>
 __device__ __forceinline__ void ingest_yuv_quad(const TmFrameDesc &d, const float *__restrict__ coef,
                                                 const double *__restrict__ tab, int qx, int qy, float (&px)[2][2][3])

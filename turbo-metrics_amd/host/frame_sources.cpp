@@ -935,6 +935,7 @@ std::unique_ptr<FrameSource> open_y4m_stream(FILE *f, std::string header, bool s
     uint32_t w = 0, h = 0;
     int bits = 8;
     std::string cs = "420";
+    uint32_t fps_num = 0, fps_den = 0;
     bool full = hints.full_range;
     std::string tok;
     while (ss >> tok) {
@@ -942,6 +943,10 @@ std::unique_ptr<FrameSource> open_y4m_stream(FILE *f, std::string header, bool s
             if (tok[0] == 'W') w = (uint32_t)std::stoul(tok.substr(1));
             else if (tok[0] == 'H') h = (uint32_t)std::stoul(tok.substr(1));
             else if (tok[0] == 'C') cs = tok.substr(1);
+            else if (tok[0] == 'F') { // F<num>:<den>
+                const size_t colon = tok.find(':');
+                if (colon != std::string::npos) { fps_num = (uint32_t)std::stoul(tok.substr(1, colon - 1)); fps_den = (uint32_t)std::stoul(tok.substr(colon + 1)); }
+            }
             else if (tok == "XCOLORRANGE=FULL") full = true;
             else if (tok == "XCOLORRANGE=LIMITED") full = false;
         } catch (const std::logic_error &) { fail("Y4M: malformed stream header"); }
@@ -964,6 +969,7 @@ std::unique_ptr<FrameSource> open_y4m_stream(FILE *f, std::string header, bool s
     auto src = std::make_unique<YuvStreamSource>(f, true, w, h, bits, cc, full ? ColorRange::Full : ColorRange::Limited, count,
                                                  "I420" + (bits > 8 ? "p" + std::to_string(bits) : std::string()));
     src->set_prefix(std::move(prefix));
+    if (fps_num > 0 && fps_den > 0) src->set_frame_rate(fps_num, fps_den);
     return src;
 }
 

@@ -109,6 +109,8 @@ public:
     void prepare() override; // the whole ring, page-locked, before the first frame is asked for
     // bytes that were read from the stream before this source took it over (the format probe of a pipe)
     void set_prefix(std::vector<unsigned char> bytes);
+    std::pair<uint32_t, uint32_t> frame_rate() const override { return fps_; }
+    void set_frame_rate(uint32_t num, uint32_t den) { fps_ = {num, den}; }
 
 private:
     size_t read_bytes(unsigned char *dst, size_t n);
@@ -123,6 +125,7 @@ private:
     ColorRange cr_;
     size_t frame_count_;
     std::string codec_;
+    std::pair<uint32_t, uint32_t> fps_{0, 0};
     size_t planar_bytes_ = 0;                   // one picture in the STREAM
     bool pack10_ = false;                       // 10-bit pictures are packed three samples to a word on their way into the ring
     size_t slot_bytes_ = 0, row_y_ = 0, row_c_ = 0; // one picture in the RING (packed: rows of whole 512-byte blocks), its row pitches

@@ -46,7 +46,7 @@ void usage(std::ostream &os)
           "  <REFERENCE>  Reference media (PNG / PPM / PFM image, Y4M or raw planar YUV, IVF / Matroska video through TM_DECODER). Use `-` to read from stdin\n"
           "  <DISTORTED>  Distorted media. Use `-` to read from stdin\n\n"
           "Options:\n"
-          "  -m, --metrics <METRICS>    Select the metrics to compute [possible values: psnr, ssim, msssim, ssimulacra2]\n"
+          "  -m, --metrics <METRICS>    Select the metrics to compute [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr]\n"
           "      --every <EVERY>        Only compute metrics every few frames [default: 0]\n"
           "      --skip <SKIP>          Index of the first frame to start computing at [default: 0]\n"
           "      --skip-ref <SKIP_REF>  Index of the first reference frame, additive with `skip` [default: 0]\n"
@@ -66,6 +66,7 @@ void usage(std::ostream &os)
           "      --width <W> --height <H> [--bits 8|10|12|16]   headerless planar 4:2:0 input\n"
           "      --color-primaries <N> --matrix-coefficients <N> --transfer-characteristics <N>   H.273 codes (1, 5, 6; 2 = by height)\n"
           "      --full-range           the YUV input is full range (unsupported by the reference and here)\n"
+          "      --xpsnr-fps <N[/D]>    frame rate that picks XPSNR's temporal order (below 32: first order) [default: the Y4M F token, else 25]\n"
           "  -h, --help                 Print help\n"
           "  -V, --version              Print version\n";
 }
@@ -129,6 +130,7 @@ int main(int argc, char **argv)
     Output output = Output::Default;
     SourceHints hints;
     uint32_t batch = 0 /* 0: chosen from the picture size */, device = 0, devices = 1, ranks = 0 /* 0: not asked for */, in_flight_pairs = 2;
+    uint32_t xpsnr_fps_num = 0, xpsnr_fps_den = 1; // --xpsnr-fps (0: not given)
     bool pipeline = true, full_sums = false, in_flight_given = false;
     enum class Loop { Batched, Reference, Deferred } loop = Loop::Batched;
     std::vector<std::pair<int, long long>> tune;
@@ -161,11 +163,13 @@ int main(int argc, char **argv)
             if (!value(s)) return bad("a value is required for '--metrics <METRICS>' but none was supplied");
             if (s == "psnr") metrics.psnr = true; else if (s == "ssim") metrics.ssim = true; else if (s == "msssim") metrics.msssim = true;
             else if (s == "ssimulacra2") metrics.ssimulacra2 = true;
+            else if (s == "xpsnr") metrics.xpsnr = true;
             else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2]");
         } else if (a.rfind("-m", 0) == 0 && a.size() > 2 && a[1] == 'm') { // -mpsnr
             const std::string s = a.substr(2);
             if (s == "psnr") metrics.psnr = true; else if (s == "ssim") metrics.ssim = true; else if (s == "msssim") metrics.msssim = true;
             else if (s == "ssimulacra2") metrics.ssimulacra2 = true;
+            else if (s == "xpsnr") metrics.xpsnr = true;
             else return bad("invalid value '" + s + "' for '--metrics <METRICS>'");
         } else if (a == "--every") { if (!u32(opts.every)) return bad("invalid value for '--every <EVERY>'"); }
         else if (a == "--skip") { if (!u32(opts.skip)) return bad("invalid value for '--skip <SKIP>'"); }
@@ -188,6 +192,14 @@ int main(int argc, char **argv)
             else return bad("invalid value '" + s + "' for '--loop <MODE>'\n  [possible values: batched, reference, deferred]");
         }
         else if (a == "--full-sums") full_sums = true;
+        else if (a == "--xpsnr-fps") {
+            std::string v;
+            if (!value(v)) return bad("a value is required for '--xpsnr-fps <N[/D]>'");
+            const size_t sl = v.find('/');
+            if (!parse_u32(v.substr(0, sl), xpsnr_fps_num) || (sl != std::string::npos && !parse_u32(v.substr(sl + 1), xpsnr_fps_den)) ||
+                xpsnr_fps_num == 0 || xpsnr_fps_den == 0)
+                return bad("invalid value '" + v + "' for '--xpsnr-fps <N[/D]>'");
+        }
         else if (a == "--tune") { // --tune <param>=<value>: tm_engine_debug_set_param (measurements; not in the usage text)
             std::string kv; if (!value(kv) || kv.find('=') == std::string::npos) return bad("invalid value for '--tune <param>=<value>'");
             tune.emplace_back(atoi(kv.c_str()), atoll(kv.c_str() + kv.find('=') + 1));
@@ -204,6 +216,13 @@ int main(int argc, char **argv)
         else pos.push_back(a);
     }
     if (pos.size() != 2) return bad("the following required arguments were not provided:\n  <REFERENCE>\n  <DISTORTED>");
+    if (metrics.xpsnr) { // XPSNR is stateful across the frames of ONE sequence on one device
+        const char *why = opts.every > 1 ? "--every > 1 (skipped pictures never reach its temporal history)"
+                        : devices != 1 ? "--devices (shards would cut its temporal history)"
+                        : ranks > 0 ? "--ranks (shards would cut its temporal history)"
+                        : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
+        if (why) { log_line(L_ERROR, kTarget, std::string("-m xpsnr does not run with ") + why); return EXIT_FAILURE; }
+    }
 
     const bool ref_is_stdin = pos[0] == "-", dis_is_stdin = pos[1] == "-";
     if (ref_is_stdin && dis_is_stdin) {
@@ -450,7 +469,7 @@ int main(int argc, char **argv)
 
     std::unique_ptr<TurboMetrics> turbo;
     try {
-        if (metrics.mask() == 0) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
+        if (metrics.mask() == 0 && !metrics.xpsnr) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
         // a source that knows its length never needs more slots than it has pairs (a single image pair: one slot, one engine)
         const size_t known = std::min(source_ref->frame_count(), source_dis->frame_count());
         if (batch == 0) batch = auto_batch(source_ref->width(), source_ref->height());
@@ -460,6 +479,11 @@ int main(int argc, char **argv)
         if (known > 0 && known < 20000) tm_set_placement_candidates(1);
         turbo = std::make_unique<TurboMetrics>(source_ref->width(), source_ref->height(), metrics, batch, pipeline);
         if (full_sums) turbo->set_full_sums(true);
+        if (metrics.xpsnr) { // --xpsnr-fps, else the Y4M frame rate, else ffmpeg's rawvideo default of 25 fps
+            const auto fr = source_ref->frame_rate();
+            if (xpsnr_fps_num) turbo->set_xpsnr_fps(xpsnr_fps_num, xpsnr_fps_den);
+            else if (fr.first && fr.second) turbo->set_xpsnr_fps(fr.first, fr.second);
+        }
         for (auto &t : tune) if (t.first < 100) turbo->debug_set_param(t.first, t.second);
         // --loop deferred: every engine of the turn exists before the clock starts (the reference allocates everything up front too,
         // ssimulacra2-cuda/src/lib.rs:21)

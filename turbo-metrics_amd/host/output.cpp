@@ -28,21 +28,23 @@ std::vector<Named> stat_fields(const Stats &s)
             {"sample_stddev", s.sample_stddev}, {"p1", s.p1}, {"p5", s.p5}, {"p50", s.p50}, {"p95", s.p95}, {"p99", s.p99}};
 }
 
-void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os)
+void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os, bool xpsnr = false)
 {
     bool first = true;
     auto put = [&](bool on, const char *n) { if (on) { os << (first ? "" : ",") << n; first = false; } };
     put(psnr, "psnr"); put(ssim, "ssim"); put(msssim, "msssim"); put(ssimu, "ssimulacra2");
+    put(xpsnr, "xpsnr_y"); put(xpsnr, "xpsnr_u"); put(xpsnr, "xpsnr_v");
     if (first) os << "\"\""; // csv::Writer writes an empty record as ""
     os << "\n";
 }
 
 void csv_row(const std::optional<double> &a, const std::optional<double> &b, const std::optional<double> &c, const std::optional<double> &d,
-             std::ostream &os)
+             std::ostream &os, const std::optional<double> &xy = std::nullopt, const std::optional<double> &xu = std::nullopt,
+             const std::optional<double> &xv = std::nullopt)
 {
     bool first = true;
     auto put = [&](const std::optional<double> &v) { if (v) { os << (first ? "" : ",") << display(*v); first = false; } };
-    put(a); put(b); put(c); put(d);
+    put(a); put(b); put(c); put(d); put(xy); put(xu); put(xv);
     if (first) os << "\"\"";
     os << "\n";
 }
@@ -57,6 +59,7 @@ std::string frame_scores_json(const FrameScores &r)
         first = false;
     };
     put("psnr", r.psnr); put("ssim", r.ssim); put("msssim", r.msssim); put("ssimulacra2", r.ssimulacra2);
+    put("xpsnr_y", r.xpsnr_y); put("xpsnr_u", r.xpsnr_u); put("xpsnr_v", r.xpsnr_v);
     return s + "}";
 }
 
@@ -86,13 +89,13 @@ std::string stats_json(const Stats &s, int indent, bool pretty)
 
 void output_prepare(Output o, const Metrics &m, std::ostream &os)
 {
-    if (o == Output::CSV) csv_header(m.psnr, m.ssim, m.msssim, m.ssimulacra2, os);
+    if (o == Output::CSV) csv_header(m.psnr, m.ssim, m.msssim, m.ssimulacra2, os, m.xpsnr);
 }
 
 void output_single_score(Output o, const FrameScores &r, std::ostream &os)
 {
     if (o == Output::JsonLines) os << frame_scores_json(r) << "\n";
-    else if (o == Output::CSV) csv_row(r.psnr, r.ssim, r.msssim, r.ssimulacra2, os);
+    else if (o == Output::CSV) csv_row(r.psnr, r.ssim, r.msssim, r.ssimulacra2, os, r.xpsnr_y, r.xpsnr_u, r.xpsnr_v);
 }
 
 void output_results(Output o, const MetricsResults &r, std::ostream &os)
@@ -103,6 +106,13 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
         if (r.ssim) os << "SSIM: " << stats_debug_pretty(r.ssim->stats) << "\n";
         if (r.msssim) os << "MSSSIM: " << stats_debug_pretty(r.msssim->stats) << "\n";
         if (r.ssimulacra2) os << "SSIMULACRA2: " << stats_debug_pretty(r.ssimulacra2->stats) << "\n";
+        if (r.xpsnr_y) {
+            os << "XPSNR_Y: " << stats_debug_pretty(r.xpsnr_y->stats) << "\n";
+            os << "XPSNR_U: " << stats_debug_pretty(r.xpsnr_u->stats) << "\n";
+            os << "XPSNR_V: " << stats_debug_pretty(r.xpsnr_v->stats) << "\n";
+            os << "XPSNR (sequence): y " << debug(*r.xpsnr_y->sequence) << ", u " << debug(*r.xpsnr_u->sequence) << ", v "
+               << debug(*r.xpsnr_v->sequence) << "\n";
+        }
         break;
     case Output::Json: { // serde_json::to_string_pretty: two-space indent, `"key": value`
         os << "{\n  \"frame_count\": " << r.frame_count;
@@ -110,9 +120,12 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
             if (!a) return;
             os << ",\n  \"" << n << "\": {\n    \"scores\": [";
             for (size_t i = 0; i < a->scores.size(); ++i) os << (i ? ",\n      " : "\n      ") << json_number(a->scores[i]);
-            os << (a->scores.empty() ? "]" : "\n    ]") << ",\n    \"stats\": " << stats_json(a->stats, 4, true) << "\n  }";
+            os << (a->scores.empty() ? "]" : "\n    ]") << ",\n    \"stats\": " << stats_json(a->stats, 4, true);
+            if (a->sequence) os << ",\n    \"sequence\": " << json_number(*a->sequence);
+            os << "\n  }";
         };
         put("psnr", r.psnr); put("ssim", r.ssim); put("msssim", r.msssim); put("ssimulacra2", r.ssimulacra2);
+        put("xpsnr_y", r.xpsnr_y); put("xpsnr_u", r.xpsnr_u); put("xpsnr_v", r.xpsnr_v);
         os << "\n}\n";
         break;
     }
@@ -121,14 +134,20 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
         os << "{\"frame_count\":" << s.frame_count;
         auto put = [&](const char *n, const std::optional<Stats> &st) { if (st) os << ",\"" << n << "\":" << stats_json(*st, 0, false); };
         put("psnr", s.psnr); put("ssim", s.ssim); put("msssim", s.msssim); put("ssimulacra2", s.ssimulacra2);
+        auto put_x = [&](const char *n, const std::optional<MetricAggregate> &a) { // the stats, then "sequence"
+            if (!a) return;
+            const std::string st = stats_json(a->stats, 0, false);
+            os << ",\"" << n << "\":" << st.substr(0, st.size() - 1) << ",\"sequence\":" << json_number(*a->sequence) << "}";
+        };
+        put_x("xpsnr_y", r.xpsnr_y); put_x("xpsnr_u", r.xpsnr_u); put_x("xpsnr_v", r.xpsnr_v);
         os << "}\n";
         break;
     }
     case Output::CSV:
-        csv_header((bool)r.psnr, (bool)r.ssim, (bool)r.msssim, (bool)r.ssimulacra2, os);
+        csv_header((bool)r.psnr, (bool)r.ssim, (bool)r.msssim, (bool)r.ssimulacra2, os, (bool)r.xpsnr_y);
         for (size_t i = 0; i < r.frame_count; ++i) {
             auto at = [&](const std::optional<MetricAggregate> &a) { return a ? std::optional<double>(a->scores[i]) : std::nullopt; };
-            csv_row(at(r.psnr), at(r.ssim), at(r.msssim), at(r.ssimulacra2), os);
+            csv_row(at(r.psnr), at(r.ssim), at(r.msssim), at(r.ssimulacra2), os, at(r.xpsnr_y), at(r.xpsnr_u), at(r.xpsnr_v));
         }
         break;
     }

@@ -1,7 +1,11 @@
 // turbo_metrics.cpp -- see turbo_metrics.hpp.  Host orchestration only: frame selection, batching over the engine's
 // slots, ping-pong pipelining of two engines; every number comes out of libturbometrics_hip.so.
 #include "turbo_metrics.hpp"
+#include "../../include/turbo_metrics_xpsnr.h"
 #include <dlfcn.h>
+#include <array>
+#include <cmath>
+#include <deque>
 #include <chrono>
 #include <fstream>
 #include <sched.h>
@@ -170,10 +174,122 @@ const char *to_string(TransferCharacteristic v)
 }
 const char *to_string(ColorRange v) { return v == ColorRange::Full ? "Full" : "Limited"; }
 
+// ---- XPSNR ---------------------------------------------------------------------------------------------------------
+// libturbometrics_xpsnr.so, loaded at run time (a CLI run without -m xpsnr never loads it; the host archive has no link dependency on
+// it).  Pairs are handed over as TM_MEM_HOST copies -- done before set_frame returns, so the sources' rings of page-locked surfaces and
+// the engine's upload fences are untouched -- and computed batch by batch in stream order; results wait in `ready` until the engine's
+// scores of the same pairs are drained.
+struct XpsnrRun {
+    void *lib = nullptr;
+    int (*create)(tm_xpsnr **, uint32_t, uint32_t, int, uint32_t, uint32_t, uint32_t, uint32_t) = nullptr;
+    void (*destroy)(tm_xpsnr *) = nullptr;
+    int (*set_frame)(tm_xpsnr *, uint32_t, int, const void *, const void *, const void *, size_t, size_t, int) = nullptr;
+    int (*compute_async)(tm_xpsnr *, uint32_t) = nullptr;
+    int (*sync)(tm_xpsnr *) = nullptr;
+    int (*get)(tm_xpsnr *, uint32_t, uint32_t, tm_xpsnr_frame *) = nullptr;
+    double (*sequence)(double, double, uint64_t, uint32_t, uint32_t, uint32_t) = nullptr;
+    tm_xpsnr *x = nullptr;
+    uint32_t w, h, batch, fps_num = 25, fps_den = 1; // ffmpeg's rawvideo default of 25 fps when nothing else is known
+    int layout = -1;
+    uint32_t bits = 8, filled = 0;
+    std::deque<std::array<double, 3>> ready;
+    double sum_sqrt[3] = {0, 0, 0}, sum_x[3] = {0, 0, 0};
+    uint64_t frames = 0;
+
+    XpsnrRun(uint32_t w_, uint32_t h_, uint32_t batch_) : w(w_), h(h_), batch(batch_)
+    {
+        const char *path = getenv("TM_XPSNR_LIB");
+        lib = dlopen(path ? path : "libturbometrics_xpsnr.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("-m xpsnr needs libturbometrics_xpsnr.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_xpsnr_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_xpsnr_destroy");
+        set_frame = (decltype(set_frame))dlsym(lib, "tm_xpsnr_set_frame");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_xpsnr_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_xpsnr_sync");
+        get = (decltype(get))dlsym(lib, "tm_xpsnr_get");
+        sequence = (decltype(sequence))dlsym(lib, "tm_xpsnr_sequence");
+        if (!create || !destroy || !set_frame || !compute_async || !sync || !get || !sequence)
+            throw std::runtime_error("libturbometrics_xpsnr.so does not export include/turbo_metrics_xpsnr.h");
+    }
+    ~XpsnrRun()
+    {
+        if (x) destroy(x);
+        if (lib) dlclose(lib);
+    }
+    static void layout_of(const HwFrame &f, int &layout, uint32_t &bits)
+    {
+        switch (f.kind) {
+        case HwFrame::NvDecNV12: layout = TM_XPSNR_NV12; bits = 8; return;
+        case HwFrame::NvDecP016: layout = TM_XPSNR_P016; bits = 10; return;
+        case HwFrame::Planar420: layout = TM_XPSNR_I420; bits = (uint32_t)f.bits; return;
+        case HwFrame::Planar420P10: layout = TM_XPSNR_I420P10_PACKED; bits = 10; return;
+        default: throw std::runtime_error("xpsnr needs 4:2:0 YUV input (Y4M, raw planar YUV or decoded video), not RGB images");
+        }
+    }
+    void push(const HwFrame &r, const HwFrame &d)
+    {
+        int lr, ld;
+        uint32_t br, bd;
+        layout_of(r, lr, br);
+        layout_of(d, ld, bd);
+        if (lr != ld || br != bd) throw std::runtime_error("xpsnr needs reference and distorted in the same YUV layout and bit depth");
+        if (!x) {
+            layout = lr; bits = br;
+            chk(create(&x, w, h, layout, bits, fps_num, fps_den, batch), "tm_xpsnr_create");
+        } else if (lr != layout || br != bits) {
+            throw std::runtime_error("xpsnr: the YUV layout changed inside the stream");
+        }
+        const bool bi = layout == TM_XPSNR_NV12 || layout == TM_XPSNR_P016;
+        int side = TM_SIDE_REF;
+        for (const HwFrame *f : {&r, &d}) {
+            chk(set_frame(x, filled, side, f->data, bi ? f->uv : f->u, bi ? nullptr : f->v, f->pitch, bi ? f->pitch : f->pitch_uv,
+                          f->device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_xpsnr_set_frame");
+            side = TM_SIDE_DIS;
+        }
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(x, filled), "tm_xpsnr_compute_async");
+        chk(sync(x), "tm_xpsnr_sync");
+        std::vector<tm_xpsnr_frame> out(filled);
+        chk(get(x, 0, filled, out.data()), "tm_xpsnr_get");
+        for (const tm_xpsnr_frame &f : out) {
+            for (int c = 0; c < 3; ++c) { sum_sqrt[c] += sqrt((double)f.wsse[c]); sum_x[c] += f.xpsnr[c]; }
+            ready.push_back({f.xpsnr[0], f.xpsnr[1], f.xpsnr[2]});
+            ++frames;
+        }
+        filled = 0;
+    }
+    std::array<double, 3> pop()
+    {
+        if (ready.empty()) throw std::logic_error("xpsnr: a pair's result is missing");
+        const std::array<double, 3> v = ready.front();
+        ready.pop_front();
+        return v;
+    }
+    double sequence_score(int c) const
+    {
+        const uint32_t pw = c ? (w + 1) / 2 : w, ph = c ? (h + 1) / 2 : h;
+        return sequence(sum_sqrt[c], sum_x[c], frames, pw, ph, bits);
+    }
+};
+
+void TurboMetrics::set_xpsnr_fps(uint32_t num, uint32_t den)
+{
+    if (!xp_) throw std::runtime_error("xpsnr was not selected");
+    if (num == 0 || den == 0) throw TmError(TM_ERR_INVALID_ARG, "set_xpsnr_fps");
+    xp_->fps_num = num;
+    xp_->fps_den = den;
+}
+
 // ---- engine --------------------------------------------------------------------------------------------------------
 TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metrics, uint32_t batch, bool pipeline)
     : w_(width), h_(height), batch_(batch ? batch : 1), metrics_(metrics)
 {
+    if (metrics_.xpsnr) xp_ = std::make_unique<XpsnrRun>(w_, h_, batch_);
+    if (metrics_.mask() == 0 && metrics_.xpsnr) return; // -m xpsnr alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -446,11 +562,19 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     uint32_t filled[2] = {0, 0};
     bool in_flight[2] = {false, false};
     int cur = 0;
+    std::optional<std::vector<double>> s_xp[3];
+    if (xp_)
+        for (auto &v : s_xp) v.emplace();
     auto drain = [&](int i) {
         if (!in_flight[i]) return;
-        chk(tm_engine_sync(eng_[i]), "tm_engine_sync");
+        if (eng_[i]) chk(tm_engine_sync(eng_[i]), "tm_engine_sync");
         for (uint32_t slot = 0; slot < filled[i]; ++slot) {
-            const FrameScores r = scores_of(eng_[i], slot);
+            FrameScores r = eng_[i] ? scores_of(eng_[i], slot) : FrameScores{};
+            if (xp_) { // (its batch was computed when the engine's was submitted: in stream order, ready)
+                const std::array<double, 3> v = xp_->pop();
+                r.xpsnr_y = v[0]; r.xpsnr_u = v[1]; r.xpsnr_v = v[2];
+                for (int c = 0; c < 3; ++c) s_xp[c]->push_back(v[c]);
+            }
             if (on_frame) on_frame(r);
             if (s_psnr && r.psnr) s_psnr->push_back(*r.psnr);
             if (s_ssim && r.ssim) s_ssim->push_back(*r.ssim);
@@ -463,7 +587,8 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     };
     auto submit = [&](int i) {
         if (filled[i] == 0) return;
-        chk(tm_engine_compute_async(eng_[i], filled[i]), "tm_engine_compute_async");
+        if (eng_[i]) chk(tm_engine_compute_async(eng_[i], filled[i]), "tm_engine_compute_async");
+        if (xp_) xp_->flush();
         in_flight[i] = true;
     };
 
@@ -513,7 +638,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     for (;;) {
         const bool dropped = opts.every > 1 && decode_count != 0 && decode_count % opts.every != 0; // lib.rs:391-394
         auto t0 = tick();
-        if (!dropped && kept > UPLOADS_IN_FLIGHT) { // the call below may overwrite the surfaces of pair kept - UPLOADS_IN_FLIGHT - 1
+        if (!dropped && kept > UPLOADS_IN_FLIGHT && eng_[0]) { // the call below may overwrite the surfaces of pair kept - UPLOADS_IN_FLIGHT - 1
             const Fence &f = fences[(kept - UPLOADS_IN_FLIGHT - 1) % fences.size()]; // (it has one: UPLOADS_IN_FLIGHT >= FENCE_EVERY)
             const int r = tm_engine_upload_done(f.e, f.token, 1);
             if (r < 0) chk(-r, "tm_engine_upload_done");
@@ -530,10 +655,13 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (opts.frames > 0 && decode_count >= opts.frames) break; // lib.rs:396-398
         ++decode_count;
         t0 = tick();
-        set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
-        set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
+        if (xp_) xp_->push(fref, fdis);
+        if (eng_[cur]) {
+            set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
+            set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
+        }
         ++kept;
-        if (kept - first_unfenced >= FENCE_EVERY || filled[cur] + 1 == batch_) { // (a fence covers one engine's uploads: never across a batch)
+        if (eng_[cur] && (kept - first_unfenced >= FENCE_EVERY || filled[cur] + 1 == batch_)) { // (a fence covers one engine's uploads: never across a batch)
             Fence f;
             f.e = eng_[cur];
             chk(tm_engine_upload_fence(f.e, &f.token), "tm_engine_upload_fence");
@@ -561,8 +689,15 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_))
         throw NoFramesSelected();
+    if (xp_) {
+        std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
+        for (int c = 0; c < 3; ++c) {
+            *dst[c] = MetricAggregate::from(std::move(*s_xp[c]));
+            (*dst[c])->sequence = xp_->sequence_score(c);
+        }
+    }
     if (s_psnr) res.psnr = MetricAggregate::from(std::move(*s_psnr));
     if (s_ssim) res.ssim = MetricAggregate::from(std::move(*s_ssim));
     if (s_msssim) res.msssim = MetricAggregate::from(std::move(*s_msssim));

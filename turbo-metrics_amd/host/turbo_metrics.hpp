@@ -29,6 +29,8 @@ namespace tm_host {
 
 struct Metrics {
     bool psnr = false, ssim = false, msssim = false, ssimulacra2 = false;
+    // XPSNR (include/turbo_metrics_xpsnr.h, libturbometrics_xpsnr.so): not an engine metric, so not in mask()
+    bool xpsnr = false;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -47,6 +49,7 @@ struct Options {
 struct MetricAggregate {
     std::vector<double> scores;
     Stats stats;
+    std::optional<double> sequence; // XPSNR: the sequence score (tm_xpsnr_sequence)
     static MetricAggregate from(std::vector<double> v)
     {
         MetricAggregate a;
@@ -59,6 +62,7 @@ struct MetricAggregate {
 struct MetricsResults {
     size_t frame_count = 0;
     std::optional<MetricAggregate> psnr, ssim, msssim, ssimulacra2;
+    std::optional<MetricAggregate> xpsnr_y, xpsnr_u, xpsnr_v;
 };
 
 struct MetricsStats {
@@ -78,6 +82,7 @@ struct MetricsStats {
 
 struct FrameScores {
     std::optional<double> psnr, ssim, msssim, ssimulacra2;
+    std::optional<double> xpsnr_y, xpsnr_u, xpsnr_v;
 };
 
 // ---- colour metadata (H.273 code points the reference understands, codec-bitstream/src/lib.rs:98-248) ----------
@@ -163,6 +168,8 @@ public:
     // surface pool the reference's decoder allocates when it is CREATED (cudarse-video/src/dec_simple.rs), i.e. before the CLI's clock
     // starts (turbo-metrics-cli/src/main.rs:252).  Call after set_lookahead / set_readahead; next_frame does it itself otherwise.
     virtual void prepare() {}
+    // the stream's frame rate as num / den (Y4M `F` token), {0, 0} when the source does not say
+    virtual std::pair<uint32_t, uint32_t> frame_rate() const { return {0, 0}; }
 };
 
 // CPUs this process may really use: the smallest of the hardware threads, the affinity mask and the cgroup CPU quota (a container
@@ -212,6 +219,9 @@ public:
     void debug_set_param(int param, long long value);
     // measurement: how many pairs' uploads may be in flight behind the one being read (4) and how many pairs share a fence (1)
     static void set_upload_tuning(size_t in_flight, size_t fence_every);
+    // XPSNR beside (or, with no engine metric selected, instead of) the engine: the frame rate that picks its temporal order.
+    // compute_all hands every kept pair to libturbometrics_xpsnr.so as TM_MEM_HOST copies (4:2:0 YUV frames only).
+    void set_xpsnr_fps(uint32_t num, uint32_t den);
 
     using ColorInfo = std::pair<ColorCharacteristics, ColorRange>;
     // == compute_one (lib.rs:268-360): convert both frames, compute every selected metric, block, return the scores
@@ -261,6 +271,7 @@ private:
     std::vector<uint64_t> def_pending_{0, 0};
     std::vector<std::pair<uint64_t, FrameScores>> def_done_;
     uint64_t def_next_ = 1;
+    std::unique_ptr<struct XpsnrRun> xp_;                     // metrics_.xpsnr: the sequence's XPSNR state (library created at the first pair)
     bool full_sums_ = false;                                  // settings replayed on an engine that is created later
     std::vector<std::pair<int, long long>> debug_params_;
 };
