@@ -181,3 +181,189 @@ def test_cli_xpsnr_refuses_rgb_images(tmp_path):
     b.write_bytes(ppm)
     out = _cli(str(a), str(b), "-m", "xpsnr")
     assert out.returncode != 0 and "xpsnr" in out.stderr, (out.returncode, out.stderr)
+
+
+# ---- content, dirty bytes, memory kinds and alignments, D = 16, b = 256, 130 slots, the fps boundary ------------------------------
+from tests import xpsnr_twin as T  # noqa: E402
+
+
+def _twin(w, h, bits, fps, pics):
+    seq = T.Sequence(w, h, bits, fps)
+    return [seq.push(r, d) for r, d in pics], seq
+
+
+def _hand_over(planes, mem, vec):
+    """numpy planes -> what set_pair gets.  device / pinned: torch copies; vec=False hands over views at a storage offset of one
+    element (no longer 16-byte aligned: the kernels' per-sample loads).  Device copies carry garbage past every row (the planes come
+    from layout_planes dirty= with padding) and the element before an offset view is garbage too."""
+    import torch
+    out = []
+    for p in planes:
+        t = _torch(np.ascontiguousarray(p))
+        if not vec:
+            flat = torch.full((t.numel() + 1,), 0x55, dtype=t.dtype)
+            flat[1:] = t.reshape(-1)
+            t = flat[1:].view(t.shape)
+        if mem == "device":
+            t = t.cuda() if vec else (lambda f: f[1:].view(t.shape))(flat.cuda())
+        elif mem == "pinned":
+            t = t.pin_memory() if vec else (lambda f: f[1:].view(t.shape))(flat.pin_memory())
+        elif vec:
+            t = np.ascontiguousarray(p)
+        out.append(t)
+    return out
+
+
+def _run_dirty(x, layout, w, h, bits, pics, batches, mem, vec, pad):
+    out, i = [], 0
+    keep = []
+    for n in batches:
+        for s in range(n):
+            sides = [_hand_over(U.layout_planes(layout, pics[i + s][side], w, h, bits, pad, dirty=U.dirt_seed(i + s, side)), mem, vec)
+                     for side in (0, 1)]
+            keep.append(sides)
+            x.set_pair(s, *sides)
+        x.compute(n)
+        out += x.frames(n)
+        i += n
+    return out
+
+
+@pytest.mark.parametrize("w,h,layout,bits,kind,pad", [
+    (352, 288, "i420", 10, "random", 8),     # bits above D; pitch 720 bytes: 16-byte aligned rows with vec
+    (352, 288, "p016", 12, "steps", 8),      # low bits of P016 words
+    (352, 288, "nv12", 8, "stripes", 16),
+    (390, 270, "i420p10", 10, "random", 4),  # packed bits 30-31, absent samples of the last run
+    (256, 130, "i420", 16, "checker", 8),    # D = 16 full-scale checkerboard
+    (256, 130, "p016", 16, "flat", 8),
+    (176, 144, "i420", 12, "identical", 8),  # wsse 0: +inf
+])
+def test_dirty_bytes_content_memory_kinds_and_alignment(w, h, layout, bits, kind, pad):
+    fps, batches = (60, 1), [2, 1]
+    pics = [U.pictures(w, h, n, bits, kind) for n in range(3)]
+    want, _ = _twin(w, h, bits, fps, pics)
+    with tm.Xpsnr(w, h, layout, bits, fps=fps, batch=2) as x:
+        for mem in ("host", "pinned", "device"):
+            for vec in (True, False):
+                x.reset()
+                _check(_run_dirty(x, layout, w, h, bits, pics, batches, mem, vec, pad), want)
+
+
+@pytest.mark.parametrize("w,h,layout,bits,kind", [
+    (1920, 1080, "i420", 16, "random"),
+    (3840, 2160, "p016", 16, "checker"),
+    (7680, 4320, "p016", 10, "synth"),       # b = 256: the LDS tile exactly full
+    (7680, 4320, "i420", 16, "random"),
+])
+def test_full_scale_and_the_largest_blocks(w, h, layout, bits, kind):
+    fps = (60, 1)
+    pics = [U.pictures(w, h, n, bits, kind) for n in range(2)]
+    want, _ = _twin(w, h, bits, fps, pics)
+    with tm.Xpsnr(w, h, layout, bits, fps=fps, batch=2) as x:
+        _check(_run(x, layout, w, h, bits, pics, [2], mem="device"), want)
+
+
+def test_known_answers_on_the_gpu():
+    """the hand-derived answers of tests/test_xpsnr_cpu.py: checkerboard at bval 1 and 2, period-4 stripes at bval 2"""
+    cases = [(480, 270, "nv12", 8, "checker", [(470016000, 117504000, 117504000), (528768000, 132192000, 132192000)])]
+    aa = R.avg_act(2560, 1440, 8)
+    for kind, ws in (("checker", [1 / 255, 1 / 4]), ("stripes", [1 / (9 * 255), 1 / (8 * 255)])):
+        cases.append((2560, 1440, "nv12", 8, kind,
+                      [tuple(int(n * 255 * 255 * wt * aa + 0.5) for n in (2560 * 1440, 1280 * 720, 1280 * 720)) for wt in ws]))
+    for w, h, layout, bits, kind, want in cases:
+        pics = [U.pictures(w, h, n, bits, kind) for n in range(2)]
+        with tm.Xpsnr(w, h, layout, bits, fps=(25, 1), batch=2) as x:
+            assert [f.wsse for f in _run(x, layout, w, h, bits, pics, [2], mem="device")] == want, (w, h, kind)
+
+
+def test_130_slots_in_one_compute_and_in_splits():
+    """k_xpsnr_finish on ceil(130 / 64) = 3 workgroups; 48 x 48 has b = 4 (weights, smoothing)"""
+    w, h, bits, fps = 48, 48, 8, (60, 1)
+    assert R.block_size(w, h) == 4
+    pics = [U.pictures(w, h, n, bits, "random") for n in range(130)]
+    want, _ = _twin(w, h, bits, fps, pics)
+    with tm.Xpsnr(w, h, "nv12", bits, fps=fps, batch=130) as x:
+        for batches in ([130], [65, 65], [128, 2]):
+            x.reset()
+            _check(_run(x, "nv12", w, h, bits, pics, batches), want)
+
+
+@pytest.mark.parametrize("fps", [(32, 1), (63, 2)])
+def test_the_temporal_order_at_its_boundary(fps):
+    w, h, bits = 640, 360, 10
+    pics, want, _ = _want(w, h, bits, fps, 3)
+    assert R.second_order(*fps) == (fps == (32, 1))
+    with tm.Xpsnr(w, h, "i420", bits, fps=fps, batch=3) as x:
+        _check(_run(x, "i420", w, h, bits, pics, [3], mem="device"), want)
+
+
+# ---- the CLI on 9..16-bit Y4M, headerless input, odd sizes, the read-ahead pool, partial batches, NTSC rates --------------------
+def _y4m_hi(path, w, h, pics, side, bits, fps=(25, 1), header=True):
+    """Y4M (C420p10 / p12 / p16, little-endian 16-bit words) or headerless planar frames"""
+    with open(path, "wb") as f:
+        if header:
+            f.write(f"YUV4MPEG2 W{w} H{h} F{fps[0]}:{fps[1]} Ip A1:1 C420p{bits}\n".encode())
+        for p in pics:
+            if header:
+                f.write(b"FRAME\n")
+            for pl in p[side]:
+                f.write(np.asarray(pl, "<u2" if bits > 8 else np.uint8).tobytes())
+
+
+def _cli_scores(*args, env=None):
+    out = subprocess.run([CLI, *args, "-m", "xpsnr", "--output", "json-lines"], capture_output=True, text=True, timeout=300,
+                         env=None if env is None else {**os.environ, **env})
+    assert out.returncode == 0, out.stderr
+    frames, agg = _json_lines(out)
+    return out, frames, agg
+
+
+def _cli_check(frames, agg, want, seq):
+    assert len(frames) == len(want) and agg[0]["frame_count"] == len(want)
+    for f, (_, sc) in zip(frames, want):
+        for c, k in enumerate(("xpsnr_y", "xpsnr_u", "xpsnr_v")):
+            assert f[k] == (None if math.isinf(sc[c]) else sc[c]), (f, sc)
+    for c, k in enumerate(("xpsnr_y", "xpsnr_u", "xpsnr_v")):
+        assert agg[0][k]["sequence"] == seq.sequence_scores()[c]
+
+
+@pytest.mark.parametrize("bits", [10, 12, 16])
+def test_cli_high_bit_depth_y4m(tmp_path, bits):
+    """10-bit goes through the packed ring (TM_XPSNR_I420P10_PACKED); TM_PACK10=0 hands 16-bit words over instead: same stdout"""
+    w, h, n, fps = 330, 270, 5, (25, 1)
+    pics = [U.pictures(w, h, i, bits, "random" if bits == 16 else "synth") for i in range(n)]
+    want, seq = _twin(w, h, bits, fps, pics)
+    a, b = str(tmp_path / "a.y4m"), str(tmp_path / "b.y4m")
+    _y4m_hi(a, w, h, pics, 0, bits, fps)
+    _y4m_hi(b, w, h, pics, 1, bits, fps)
+    out, frames, agg = _cli_scores(a, b, "--batch", "2")
+    _cli_check(frames, agg, want, seq)
+    if bits == 10:
+        again, _, _ = _cli_scores(a, b, "--batch", "2", env={"TM_PACK10": "0"})
+        assert again.stdout == out.stdout
+
+
+@pytest.mark.parametrize("batch", [1, 4])
+def test_cli_headerless_odd_size_partial_batches(tmp_path, batch):
+    w, h, n, bits = 161, 97, 7, 8
+    pics = [U.pictures(w, h, i, bits, "steps") for i in range(n)]
+    want, seq = _twin(w, h, bits, (25, 1), pics)
+    a, b = str(tmp_path / "a.yuv"), str(tmp_path / "b.yuv")
+    _y4m_hi(a, w, h, pics, 0, bits, header=False)
+    _y4m_hi(b, w, h, pics, 1, bits, header=False)
+    _, frames, agg = _cli_scores(a, b, "--width", str(w), "--height", str(h), "--bits", "8", "--batch", str(batch))
+    _cli_check(frames, agg, want, seq)
+
+
+@pytest.mark.parametrize("fps", [(60000, 1001), (30000, 1001)])
+def test_cli_ntsc_rates_and_the_read_ahead_pool(tmp_path, fps):
+    """F60000:1001 is second order, F30000:1001 first order; 640 x 360 (>= 256 rows) starts the read-ahead pool"""
+    w, h, n = 640, 360, 6
+    pics = [U.pictures(w, h, i, 8) for i in range(n)]
+    want, seq = _twin(w, h, 8, fps, pics)
+    assert seq.second == (fps == (60000, 1001))
+    a, b = str(tmp_path / "a.y4m"), str(tmp_path / "b.y4m")
+    _y4m(a, w, h, pics, 0, fps)
+    _y4m(b, w, h, pics, 1, fps)
+    _, frames, agg = _cli_scores(a, b, "--batch", "4")
+    _cli_check(frames, agg, want, seq)

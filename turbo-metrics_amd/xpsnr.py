@@ -9,7 +9,9 @@ import ctypes as C
 import os
 from typing import NamedTuple
 
-from . import ffi
+import numpy as np
+
+from . import ffi, synth
 from .engine import _ptr_and_mem
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -106,12 +108,49 @@ class Xpsnr:
     def mem_usage(self):
         return int(self._L.tm_xpsnr_mem_usage(self._h))
 
+    def _plane_shapes(self):
+        """(rows, elements per row) of each plane of this layout, and the element size in bytes"""
+        cw, ch = (self.w + 1) // 2, (self.h + 1) // 2
+        if self.layout in ("nv12", "p016"):
+            return [(self.h, self.w), (ch, 2 * cw)], 1 if self.layout == "nv12" else 2
+        if self.layout == "i420":
+            return [(self.h, self.w), (ch, cw), (ch, cw)], 1 if self.bits == 8 else 2
+        return [(self.h, synth.p10_row_words(self.w)), (ch, synth.p10_row_words(cw)), (ch, synth.p10_row_words(cw))], 4
+
     def set_frame(self, slot, side, planes):
+        """Checks every plane against the layout before the library sees a pointer: the plane count, the element size (unsigned
+        integers; signed 16- and 32-bit ones as views of unsigned data), 2-D shapes of at least the picture's rows x row width, a
+        column stride of 1, and one row pitch for Cb and Cr (host numpy planes are copied to one instead).  ValueError otherwise."""
+        planes = list(planes)
+        shapes, esz = self._plane_shapes()
+        if len(planes) != len(shapes):
+            raise ValueError(f"{self.layout} takes {len(shapes)} planes, got {len(planes)}")
+        for i, (p, (rows, cols)) in enumerate(zip(planes, shapes)):
+            if hasattr(p, "data_ptr"):
+                size, signed, ok = p.element_size(), p.dtype.is_signed, not (p.dtype.is_floating_point or p.dtype.is_complex
+                                                                                   or str(p.dtype) == "torch.bool")
+                shape, stride = tuple(p.shape), tuple(p.stride())
+            else:
+                if not isinstance(p, np.ndarray):
+                    raise ValueError(f"plane {i}: a numpy array or a torch tensor, got {type(p).__name__}")
+                size, signed, ok = p.itemsize, p.dtype.kind == "i", p.dtype.kind in "ui"
+                shape, stride = p.shape, tuple(s // p.itemsize for s in p.strides)
+            if not ok or size != esz or (signed and size not in (2, 4)):
+                raise ValueError(f"plane {i}: {self.layout} at {self.bits} bits takes {8 * esz}-bit unsigned elements, got {p.dtype}")
+            if len(shape) != 2 or shape[0] < rows or shape[1] < cols:
+                raise ValueError(f"plane {i}: at least {rows} x {cols} elements, got shape {shape}")
+            if stride[1] != 1 or stride[0] < cols:
+                raise ValueError(f"plane {i}: rows of contiguous elements are needed, got strides {stride}")
+        if len(planes) == 3 and not any(hasattr(p, "data_ptr") for p in planes[1:]) and planes[1].strides[0] != planes[2].strides[0]:
+            # one pitch for Cb and Cr (tm_xpsnr_set_frame takes pitch_uv once): host copies of the rows the picture uses
+            planes[1:] = [np.ascontiguousarray(p[:rows, :cols]) for p, (rows, cols) in zip(planes[1:], shapes[1:])]
         planes = [_ptr_and_mem(p) for p in planes]
         mems = {m for _, m, _ in planes}
         if len(mems) != 1:
             raise ValueError("the planes must live in the same kind of memory")
         pitch = lambda k: int(k.stride(0) * k.element_size()) if hasattr(k, "data_ptr") else int(k.strides[0])
+        if len(planes) == 3 and pitch(planes[1][2]) != pitch(planes[2][2]):
+            raise ValueError("Cb and Cr must have the same row pitch (tm_xpsnr_set_frame takes pitch_uv once)")
         self._keep[(slot, side)] = [k for _, _, k in planes]
         y, u = planes[0], planes[1]
         v = planes[2] if len(planes) > 2 else (None, None, None)
