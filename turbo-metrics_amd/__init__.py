@@ -5,11 +5,13 @@ C ABI) with a host-side mirror of the reference's operator interface.
   engine  -- TurboMetrics / Ssimulacra2 / FrameScores mirrors of the reference types
   synth   -- seeded synthetic frame generators used by bench.py and the tests
   xpsnr   -- ctypes binding of include/turbo_metrics_xpsnr.h (libturbometrics_xpsnr.so): Xpsnr, XPSNR of 4:2:0 sequences
+  motion  -- ctypes binding of include/turbo_metrics_motion.h (libturbometrics_motion.so): Motion, VMAF's integer motion of a sequence
 
 There is no CPU implementation in this package: without the HIP library (or without a gfx950 GPU)
 the operators raise.
 """
-from . import ffi, launch, shard, synth, xpsnr  # noqa: F401
+from . import ffi, launch, motion, shard, synth, xpsnr  # noqa: F401
 from .engine import (ColorMatrix, FrameScores, HwFrame, Metrics, Ssimulacra2, TmError,  # noqa: F401
                      TurboMetrics, init_hip, set_debug_log, set_placement_candidates)
 from .xpsnr import Xpsnr, XpsnrFrame  # noqa: F401,E402
+from .motion import Motion, MotionFrame  # noqa: F401,E402

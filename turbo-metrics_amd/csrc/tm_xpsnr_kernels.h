@@ -24,6 +24,7 @@
 #include "tm_platform.h"
 #include "tm_geom.h"
 #include "tm_p10.h" // the packed 10-bit addressing the engine's ingest uses
+#include "tm_sample_load.h" // TMX_F_*, tmx::Src / sample1 / load4: shared with the motion kernel
 
 #define TMX_THREADS 256
 #define TMX_BAND 32                             /* luma rows per LDS band (even: 2x2 cells never straddle two bands) */
@@ -32,8 +33,6 @@
 #define TMX_TILE_W (TMX_MAX_B + 8)              /* LDS tile columns: x0 - 4 .. x0 + bw + 4, whole groups of 4 */
 #define TMX_TILE_H (TMX_BAND + 2 * TMX_HALO)
 
-// sample formats of one plane as the loader reads it
-enum { TMX_F_U8 = 0, TMX_F_U16_MSB = 1, TMX_F_U16_LOW = 2, TMX_F_P10 = 3, TMX_F_HIST = 4 };
 
 // one picture of a slot: luma plane, then Cb / Cr (p1 = interleaved CbCr of the biplanar layouts, p2 unused there)
 struct TmXpsnrDesc {
@@ -131,55 +130,6 @@ __device__ __forceinline__ bool tm_xpsnr_wave_sum5(unsigned long long (&v)[5])
 #endif
 
 namespace tmx {
-
-// samples x .. x+3 of row y of a plane (x a multiple of 4); samples at or beyond `lim` read as 0
-struct Src {
-    const char *p;
-    unsigned long long pitch;
-    int fmt;
-    int vec;
-};
-
-__device__ __forceinline__ unsigned sample1(const char *row, int fmt, int x, int shift, unsigned mask)
-{
-    switch (fmt) {
-    case TMX_F_U8: return (unsigned)((const unsigned char *)row)[x];
-    case TMX_F_U16_MSB: return (unsigned)((const unsigned short *)row)[x] >> shift;
-    case TMX_F_U16_LOW: return (unsigned)((const unsigned short *)row)[x] & mask;
-    case TMX_F_P10: return tmk::p10_sample(row, (unsigned)x);
-    default: return (unsigned)((const unsigned short *)row)[x];
-    }
-}
-
-__device__ __forceinline__ void load4(const Src &s, int x, int y, int lim, int shift, unsigned mask, unsigned (&v)[4])
-{
-    const char *row = s.p + (size_t)y * s.pitch;
-    if (s.vec && x + 4 <= lim) {
-        switch (s.fmt) {
-        case TMX_F_U8: {
-            const unsigned q = *(const unsigned *)(row + x);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = (q >> (8 * k)) & 255u;
-            return;
-        }
-        case TMX_F_P10: {
-            const uint4 q = *(const uint4 *)(row + tmk::p10_word_offset((unsigned)x));
-            const unsigned sh = tmk::p10_shift((unsigned)x);
-            v[0] = (q.x >> sh) & 1023u; v[1] = (q.y >> sh) & 1023u; v[2] = (q.z >> sh) & 1023u; v[3] = (q.w >> sh) & 1023u;
-            return;
-        }
-        default: { // 16-bit samples: two dwords
-            const uint2 q = *(const uint2 *)(row + 2 * x);
-            const unsigned r[4] = {q.x & 0xFFFFu, q.x >> 16, q.y & 0xFFFFu, q.y >> 16};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = s.fmt == TMX_F_U16_MSB ? r[k] >> shift : (s.fmt == TMX_F_U16_LOW ? r[k] & mask : r[k]);
-            return;
-        }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = x + k < lim ? sample1(row, s.fmt, x + k, shift, mask) : 0u;
-}
 
 // chroma samples cx .. cx+3 of component c (0 = Cb, 1 = Cr) of an interleaved CbCr row (NV12 / P016)
 __device__ __forceinline__ void load4_cbcr(const Src &s, int c, int cx, int cy, int lim, int shift, unsigned (&v)[4])

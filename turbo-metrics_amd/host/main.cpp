@@ -66,6 +66,7 @@ void usage(std::ostream &os)
           "      --width <W> --height <H> [--bits 8|10|12|16]   headerless planar 4:2:0 input\n"
           "      --color-primaries <N> --matrix-coefficients <N> --transfer-characteristics <N>   H.273 codes (1, 5, 6; 2 = by height)\n"
           "      --full-range           the YUV input is full range (unsupported by the reference and here)\n"
+          "      --motion               also compute VMAF's integer motion / motion2 of the REFERENCE stream (YUV inputs; runs beside -m or alone)\n"
           "      --xpsnr-fps <N[/D]>    frame rate that picks XPSNR's temporal order (below 32: first order) [default: the Y4M F token, else 25]\n"
           "  -h, --help                 Print help\n"
           "  -V, --version              Print version\n";
@@ -192,6 +193,7 @@ int main(int argc, char **argv)
             else return bad("invalid value '" + s + "' for '--loop <MODE>'\n  [possible values: batched, reference, deferred]");
         }
         else if (a == "--full-sums") full_sums = true;
+        else if (a == "--motion") metrics.motion = true;
         else if (a == "--xpsnr-fps") {
             std::string v;
             if (!value(v)) return bad("a value is required for '--xpsnr-fps <N[/D]>'");
@@ -222,6 +224,14 @@ int main(int argc, char **argv)
                         : ranks > 0 ? "--ranks (shards would cut its temporal history)"
                         : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
         if (why) { log_line(L_ERROR, kTarget, std::string("-m xpsnr does not run with ") + why); return EXIT_FAILURE; }
+    }
+
+    if (metrics.motion) { // motion compares consecutive pictures of ONE sequence on one device
+        const char *why = opts.every > 1 ? "--every > 1 (skipped pictures would never reach its history)"
+                        : devices != 1 ? "--devices (shards would cut its history)"
+                        : ranks > 0 ? "--ranks (shards would cut its history)"
+                        : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
+        if (why) { log_line(L_ERROR, kTarget, std::string("--motion does not run with ") + why); return EXIT_FAILURE; }
     }
 
     const bool ref_is_stdin = pos[0] == "-", dis_is_stdin = pos[1] == "-";
@@ -469,7 +479,7 @@ int main(int argc, char **argv)
 
     std::unique_ptr<TurboMetrics> turbo;
     try {
-        if (metrics.mask() == 0 && !metrics.xpsnr) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
+        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
         // a source that knows its length never needs more slots than it has pairs (a single image pair: one slot, one engine)
         const size_t known = std::min(source_ref->frame_count(), source_dis->frame_count());
         if (batch == 0) batch = auto_batch(source_ref->width(), source_ref->height());

@@ -28,23 +28,25 @@ std::vector<Named> stat_fields(const Stats &s)
             {"sample_stddev", s.sample_stddev}, {"p1", s.p1}, {"p5", s.p5}, {"p50", s.p50}, {"p95", s.p95}, {"p99", s.p99}};
 }
 
-void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os, bool xpsnr = false)
+void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os, bool xpsnr = false, bool motion = false)
 {
     bool first = true;
     auto put = [&](bool on, const char *n) { if (on) { os << (first ? "" : ",") << n; first = false; } };
     put(psnr, "psnr"); put(ssim, "ssim"); put(msssim, "msssim"); put(ssimu, "ssimulacra2");
     put(xpsnr, "xpsnr_y"); put(xpsnr, "xpsnr_u"); put(xpsnr, "xpsnr_v");
+    put(motion, "motion"); put(motion, "motion2");
     if (first) os << "\"\""; // csv::Writer writes an empty record as ""
     os << "\n";
 }
 
 void csv_row(const std::optional<double> &a, const std::optional<double> &b, const std::optional<double> &c, const std::optional<double> &d,
              std::ostream &os, const std::optional<double> &xy = std::nullopt, const std::optional<double> &xu = std::nullopt,
-             const std::optional<double> &xv = std::nullopt)
+             const std::optional<double> &xv = std::nullopt, const std::optional<double> &mo = std::nullopt,
+             const std::optional<double> &mo2 = std::nullopt)
 {
     bool first = true;
     auto put = [&](const std::optional<double> &v) { if (v) { os << (first ? "" : ",") << display(*v); first = false; } };
-    put(a); put(b); put(c); put(d); put(xy); put(xu); put(xv);
+    put(a); put(b); put(c); put(d); put(xy); put(xu); put(xv); put(mo); put(mo2);
     if (first) os << "\"\"";
     os << "\n";
 }
@@ -60,6 +62,7 @@ std::string frame_scores_json(const FrameScores &r)
     };
     put("psnr", r.psnr); put("ssim", r.ssim); put("msssim", r.msssim); put("ssimulacra2", r.ssimulacra2);
     put("xpsnr_y", r.xpsnr_y); put("xpsnr_u", r.xpsnr_u); put("xpsnr_v", r.xpsnr_v);
+    put("motion", r.motion); put("motion2", r.motion2);
     return s + "}";
 }
 
@@ -89,13 +92,13 @@ std::string stats_json(const Stats &s, int indent, bool pretty)
 
 void output_prepare(Output o, const Metrics &m, std::ostream &os)
 {
-    if (o == Output::CSV) csv_header(m.psnr, m.ssim, m.msssim, m.ssimulacra2, os, m.xpsnr);
+    if (o == Output::CSV) csv_header(m.psnr, m.ssim, m.msssim, m.ssimulacra2, os, m.xpsnr, m.motion);
 }
 
 void output_single_score(Output o, const FrameScores &r, std::ostream &os)
 {
     if (o == Output::JsonLines) os << frame_scores_json(r) << "\n";
-    else if (o == Output::CSV) csv_row(r.psnr, r.ssim, r.msssim, r.ssimulacra2, os, r.xpsnr_y, r.xpsnr_u, r.xpsnr_v);
+    else if (o == Output::CSV) csv_row(r.psnr, r.ssim, r.msssim, r.ssimulacra2, os, r.xpsnr_y, r.xpsnr_u, r.xpsnr_v, r.motion, r.motion2);
 }
 
 void output_results(Output o, const MetricsResults &r, std::ostream &os)
@@ -113,6 +116,8 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
             os << "XPSNR (sequence): y " << debug(*r.xpsnr_y->sequence) << ", u " << debug(*r.xpsnr_u->sequence) << ", v "
                << debug(*r.xpsnr_v->sequence) << "\n";
         }
+        if (r.motion) os << "MOTION: " << stats_debug_pretty(r.motion->stats) << "\n";
+        if (r.motion2) os << "MOTION2: " << stats_debug_pretty(r.motion2->stats) << "\n";
         break;
     case Output::Json: { // serde_json::to_string_pretty: two-space indent, `"key": value`
         os << "{\n  \"frame_count\": " << r.frame_count;
@@ -126,6 +131,7 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
         };
         put("psnr", r.psnr); put("ssim", r.ssim); put("msssim", r.msssim); put("ssimulacra2", r.ssimulacra2);
         put("xpsnr_y", r.xpsnr_y); put("xpsnr_u", r.xpsnr_u); put("xpsnr_v", r.xpsnr_v);
+        put("motion", r.motion); put("motion2", r.motion2);
         os << "\n}\n";
         break;
     }
@@ -140,14 +146,16 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
             os << ",\"" << n << "\":" << st.substr(0, st.size() - 1) << ",\"sequence\":" << json_number(*a->sequence) << "}";
         };
         put_x("xpsnr_y", r.xpsnr_y); put_x("xpsnr_u", r.xpsnr_u); put_x("xpsnr_v", r.xpsnr_v);
+        if (r.motion) put("motion", r.motion->stats);
+        if (r.motion2) put("motion2", r.motion2->stats);
         os << "}\n";
         break;
     }
     case Output::CSV:
-        csv_header((bool)r.psnr, (bool)r.ssim, (bool)r.msssim, (bool)r.ssimulacra2, os, (bool)r.xpsnr_y);
+        csv_header((bool)r.psnr, (bool)r.ssim, (bool)r.msssim, (bool)r.ssimulacra2, os, (bool)r.xpsnr_y, (bool)r.motion);
         for (size_t i = 0; i < r.frame_count; ++i) {
             auto at = [&](const std::optional<MetricAggregate> &a) { return a ? std::optional<double>(a->scores[i]) : std::nullopt; };
-            csv_row(at(r.psnr), at(r.ssim), at(r.msssim), at(r.ssimulacra2), os, at(r.xpsnr_y), at(r.xpsnr_u), at(r.xpsnr_v));
+            csv_row(at(r.psnr), at(r.ssim), at(r.msssim), at(r.ssimulacra2), os, at(r.xpsnr_y), at(r.xpsnr_u), at(r.xpsnr_v), at(r.motion), at(r.motion2));
         }
         break;
     }

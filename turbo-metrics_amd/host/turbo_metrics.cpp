@@ -2,6 +2,7 @@
 // slots, ping-pong pipelining of two engines; every number comes out of libturbometrics_hip.so.
 #include "turbo_metrics.hpp"
 #include "../../include/turbo_metrics_xpsnr.h"
+#include "../../include/turbo_metrics_motion.h"
 #include <dlfcn.h>
 #include <array>
 #include <cmath>
@@ -276,6 +277,84 @@ struct XpsnrRun {
     }
 };
 
+// ---- motion --------------------------------------------------------------------------------------------------------
+// libturbometrics_motion.so, loaded at run time like the XPSNR library (a CLI run without --motion never loads it).  The REFERENCE
+// picture of every kept pair is handed over as a TM_MEM_HOST copy and computed batch by batch in stream order; a picture's motion
+// waits in `ready` until the engine's scores of the same pair are drained.
+struct MotionRun {
+    void *lib = nullptr;
+    int (*create)(tm_motion **, uint32_t, uint32_t, int, uint32_t, uint32_t) = nullptr;
+    void (*destroy)(tm_motion *) = nullptr;
+    int (*set_frame)(tm_motion *, uint32_t, const void *, size_t, int) = nullptr;
+    int (*compute_async)(tm_motion *, uint32_t) = nullptr;
+    int (*sync)(tm_motion *) = nullptr;
+    int (*get)(tm_motion *, uint32_t, uint32_t, tm_motion_frame *) = nullptr;
+    double (*motion2)(double, double) = nullptr;
+    tm_motion *m = nullptr;
+    uint32_t w, h, batch;
+    int layout = -1;
+    uint32_t bits = 8, filled = 0;
+    std::deque<double> ready;
+
+    MotionRun(uint32_t w_, uint32_t h_, uint32_t batch_) : w(w_), h(h_), batch(batch_)
+    {
+        const char *path = getenv("TM_MOTION_LIB");
+        lib = dlopen(path ? path : "libturbometrics_motion.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("--motion needs libturbometrics_motion.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_motion_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_motion_destroy");
+        set_frame = (decltype(set_frame))dlsym(lib, "tm_motion_set_frame");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_motion_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_motion_sync");
+        get = (decltype(get))dlsym(lib, "tm_motion_get");
+        motion2 = (decltype(motion2))dlsym(lib, "tm_motion2");
+        if (!create || !destroy || !set_frame || !compute_async || !sync || !get || !motion2)
+            throw std::runtime_error("libturbometrics_motion.so does not export include/turbo_metrics_motion.h");
+    }
+    ~MotionRun()
+    {
+        if (m) destroy(m);
+        if (lib) dlclose(lib);
+    }
+    void push(const HwFrame &r)
+    {
+        int l;
+        uint32_t b;
+        switch (r.kind) {
+        case HwFrame::NvDecNV12: l = TM_MOTION_Y8; b = 8; break;
+        case HwFrame::NvDecP016: l = TM_MOTION_Y16_MSB; b = 10; break;
+        case HwFrame::Planar420: b = (uint32_t)r.bits; l = b == 8 ? TM_MOTION_Y8 : TM_MOTION_Y16_LOW; break;
+        case HwFrame::Planar420P10: l = TM_MOTION_Y10_PACKED; b = 10; break;
+        default: throw std::runtime_error("motion needs YUV input (Y4M, raw planar YUV or decoded video), not RGB images");
+        }
+        if (!m) {
+            layout = l; bits = b;
+            chk(create(&m, w, h, layout, bits, batch), "tm_motion_create");
+        } else if (l != layout || b != bits) {
+            throw std::runtime_error("motion: the YUV layout changed inside the stream");
+        }
+        chk(set_frame(m, filled, r.data, r.pitch, r.device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_motion_set_frame");
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(m, filled), "tm_motion_compute_async");
+        chk(sync(m), "tm_motion_sync");
+        std::vector<tm_motion_frame> out(filled);
+        chk(get(m, 0, filled, out.data()), "tm_motion_get");
+        for (const tm_motion_frame &f : out) ready.push_back(f.motion);
+        filled = 0;
+    }
+    double pop()
+    {
+        if (ready.empty()) throw std::logic_error("motion: a picture's result is missing");
+        const double v = ready.front();
+        ready.pop_front();
+        return v;
+    }
+};
+
 void TurboMetrics::set_xpsnr_fps(uint32_t num, uint32_t den)
 {
     if (!xp_) throw std::runtime_error("xpsnr was not selected");
@@ -289,7 +368,8 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
     : w_(width), h_(height), batch_(batch ? batch : 1), metrics_(metrics)
 {
     if (metrics_.xpsnr) xp_ = std::make_unique<XpsnrRun>(w_, h_, batch_);
-    if (metrics_.mask() == 0 && metrics_.xpsnr) return; // -m xpsnr alone: no SSIMULACRA2 / PSNR engine at all
+    if (metrics_.motion) mo_ = std::make_unique<MotionRun>(w_, h_, batch_);
+    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion)) return; // -m xpsnr or --motion alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -565,6 +645,19 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     std::optional<std::vector<double>> s_xp[3];
     if (xp_)
         for (auto &v : s_xp) v.emplace();
+    // --motion: motion2 of a pair needs the next pair's motion, so a pair's row is held until the next one is drained (or the stream ends)
+    std::optional<std::vector<double>> s_mo, s_mo2;
+    if (mo_) { s_mo.emplace(); s_mo2.emplace(); }
+    std::optional<FrameScores> held;
+    auto emit = [&](const FrameScores &r) {
+        if (on_frame) on_frame(r);
+        if (s_psnr && r.psnr) s_psnr->push_back(*r.psnr);
+        if (s_ssim && r.ssim) s_ssim->push_back(*r.ssim);
+        if (s_msssim && r.msssim) s_msssim->push_back(*r.msssim);
+        if (s_ssimu && r.ssimulacra2) s_ssimu->push_back(*r.ssimulacra2);
+        if (s_mo) { s_mo->push_back(*r.motion); s_mo2->push_back(*r.motion2); }
+        ++compute_count;
+    };
     auto drain = [&](int i) {
         if (!in_flight[i]) return;
         if (eng_[i]) chk(tm_engine_sync(eng_[i]), "tm_engine_sync");
@@ -575,12 +668,16 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
                 r.xpsnr_y = v[0]; r.xpsnr_u = v[1]; r.xpsnr_v = v[2];
                 for (int c = 0; c < 3; ++c) s_xp[c]->push_back(v[c]);
             }
-            if (on_frame) on_frame(r);
-            if (s_psnr && r.psnr) s_psnr->push_back(*r.psnr);
-            if (s_ssim && r.ssim) s_ssim->push_back(*r.ssim);
-            if (s_msssim && r.msssim) s_msssim->push_back(*r.msssim);
-            if (s_ssimu && r.ssimulacra2) s_ssimu->push_back(*r.ssimulacra2);
-            ++compute_count;
+            if (mo_) {
+                r.motion = mo_->pop();
+                if (held) {
+                    held->motion2 = mo_->motion2(*held->motion, *r.motion);
+                    emit(*held);
+                }
+                held = r;
+            } else {
+                emit(r);
+            }
         }
         in_flight[i] = false;
         filled[i] = 0;
@@ -589,6 +686,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (filled[i] == 0) return;
         if (eng_[i]) chk(tm_engine_compute_async(eng_[i], filled[i]), "tm_engine_compute_async");
         if (xp_) xp_->flush();
+        if (mo_) mo_->flush();
         in_flight[i] = true;
     };
 
@@ -656,6 +754,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         ++decode_count;
         t0 = tick();
         if (xp_) xp_->push(fref, fdis);
+        if (mo_) mo_->push(fref);
         if (eng_[cur]) {
             set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
             set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
@@ -685,11 +784,16 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     submit(cur);
     if (eng_[1]) drain(cur ^ 1);
     drain(cur);
+    if (held) { // the last picture of the stream: its motion2 is its motion
+        held->motion2 = held->motion;
+        emit(*held);
+        held.reset();
+    }
     if (decode_count_out) *decode_count_out = decode_count;
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_))
         throw NoFramesSelected();
     if (xp_) {
         std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
@@ -697,6 +801,10 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
             *dst[c] = MetricAggregate::from(std::move(*s_xp[c]));
             (*dst[c])->sequence = xp_->sequence_score(c);
         }
+    }
+    if (s_mo) {
+        res.motion = MetricAggregate::from(std::move(*s_mo));
+        res.motion2 = MetricAggregate::from(std::move(*s_mo2));
     }
     if (s_psnr) res.psnr = MetricAggregate::from(std::move(*s_psnr));
     if (s_ssim) res.ssim = MetricAggregate::from(std::move(*s_ssim));

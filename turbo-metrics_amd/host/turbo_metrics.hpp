@@ -31,6 +31,8 @@ struct Metrics {
     bool psnr = false, ssim = false, msssim = false, ssimulacra2 = false;
     // XPSNR (include/turbo_metrics_xpsnr.h, libturbometrics_xpsnr.so): not an engine metric, so not in mask()
     bool xpsnr = false;
+    // VMAF's integer motion of the REFERENCE stream (include/turbo_metrics_motion.h, libturbometrics_motion.so): the CLI's --motion
+    bool motion = false;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -63,6 +65,7 @@ struct MetricsResults {
     size_t frame_count = 0;
     std::optional<MetricAggregate> psnr, ssim, msssim, ssimulacra2;
     std::optional<MetricAggregate> xpsnr_y, xpsnr_u, xpsnr_v;
+    std::optional<MetricAggregate> motion, motion2; // their means are the sequence scores
 };
 
 struct MetricsStats {
@@ -83,6 +86,7 @@ struct MetricsStats {
 struct FrameScores {
     std::optional<double> psnr, ssim, msssim, ssimulacra2;
     std::optional<double> xpsnr_y, xpsnr_u, xpsnr_v;
+    std::optional<double> motion, motion2;
 };
 
 // ---- colour metadata (H.273 code points the reference understands, codec-bitstream/src/lib.rs:98-248) ----------
@@ -272,6 +276,7 @@ private:
     std::vector<std::pair<uint64_t, FrameScores>> def_done_;
     uint64_t def_next_ = 1;
     std::unique_ptr<struct XpsnrRun> xp_;                     // metrics_.xpsnr: the sequence's XPSNR state (library created at the first pair)
+    std::unique_ptr<struct MotionRun> mo_;                    // metrics_.motion: the reference stream's motion state (likewise)
     bool full_sums_ = false;                                  // settings replayed on an engine that is created later
     std::vector<std::pair<int, long long>> debug_params_;
 };
