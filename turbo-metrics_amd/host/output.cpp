@@ -28,13 +28,14 @@ std::vector<Named> stat_fields(const Stats &s)
             {"sample_stddev", s.sample_stddev}, {"p1", s.p1}, {"p5", s.p5}, {"p50", s.p50}, {"p95", s.p95}, {"p99", s.p99}};
 }
 
-void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os, bool xpsnr = false, bool motion = false)
+void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os, bool xpsnr = false, bool motion = false, bool vif = false)
 {
     bool first = true;
     auto put = [&](bool on, const char *n) { if (on) { os << (first ? "" : ",") << n; first = false; } };
     put(psnr, "psnr"); put(ssim, "ssim"); put(msssim, "msssim"); put(ssimu, "ssimulacra2");
     put(xpsnr, "xpsnr_y"); put(xpsnr, "xpsnr_u"); put(xpsnr, "xpsnr_v");
     put(motion, "motion"); put(motion, "motion2");
+    put(vif, "vif_scale0"); put(vif, "vif_scale1"); put(vif, "vif_scale2"); put(vif, "vif_scale3"); put(vif, "vif");
     if (first) os << "\"\""; // csv::Writer writes an empty record as ""
     os << "\n";
 }
@@ -42,11 +43,13 @@ void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os,
 void csv_row(const std::optional<double> &a, const std::optional<double> &b, const std::optional<double> &c, const std::optional<double> &d,
              std::ostream &os, const std::optional<double> &xy = std::nullopt, const std::optional<double> &xu = std::nullopt,
              const std::optional<double> &xv = std::nullopt, const std::optional<double> &mo = std::nullopt,
-             const std::optional<double> &mo2 = std::nullopt)
+             const std::optional<double> &mo2 = std::nullopt, const std::optional<double> *vif5 = nullptr)
 {
     bool first = true;
     auto put = [&](const std::optional<double> &v) { if (v) { os << (first ? "" : ",") << display(*v); first = false; } };
     put(a); put(b); put(c); put(d); put(xy); put(xu); put(xv); put(mo); put(mo2);
+    if (vif5)
+        for (int k = 0; k < 5; ++k) put(vif5[k]);
     if (first) os << "\"\"";
     os << "\n";
 }
@@ -63,6 +66,8 @@ std::string frame_scores_json(const FrameScores &r)
     put("psnr", r.psnr); put("ssim", r.ssim); put("msssim", r.msssim); put("ssimulacra2", r.ssimulacra2);
     put("xpsnr_y", r.xpsnr_y); put("xpsnr_u", r.xpsnr_u); put("xpsnr_v", r.xpsnr_v);
     put("motion", r.motion); put("motion2", r.motion2);
+    put("vif_scale0", r.vif_scale[0]); put("vif_scale1", r.vif_scale[1]); put("vif_scale2", r.vif_scale[2]); put("vif_scale3", r.vif_scale[3]);
+    put("vif", r.vif);
     return s + "}";
 }
 
@@ -92,13 +97,16 @@ std::string stats_json(const Stats &s, int indent, bool pretty)
 
 void output_prepare(Output o, const Metrics &m, std::ostream &os)
 {
-    if (o == Output::CSV) csv_header(m.psnr, m.ssim, m.msssim, m.ssimulacra2, os, m.xpsnr, m.motion);
+    if (o == Output::CSV) csv_header(m.psnr, m.ssim, m.msssim, m.ssimulacra2, os, m.xpsnr, m.motion, m.vif);
 }
 
 void output_single_score(Output o, const FrameScores &r, std::ostream &os)
 {
     if (o == Output::JsonLines) os << frame_scores_json(r) << "\n";
-    else if (o == Output::CSV) csv_row(r.psnr, r.ssim, r.msssim, r.ssimulacra2, os, r.xpsnr_y, r.xpsnr_u, r.xpsnr_v, r.motion, r.motion2);
+    else if (o == Output::CSV) {
+        const std::optional<double> v5[5] = {r.vif_scale[0], r.vif_scale[1], r.vif_scale[2], r.vif_scale[3], r.vif};
+        csv_row(r.psnr, r.ssim, r.msssim, r.ssimulacra2, os, r.xpsnr_y, r.xpsnr_u, r.xpsnr_v, r.motion, r.motion2, v5);
+    }
 }
 
 void output_results(Output o, const MetricsResults &r, std::ostream &os)
@@ -118,6 +126,10 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
         }
         if (r.motion) os << "MOTION: " << stats_debug_pretty(r.motion->stats) << "\n";
         if (r.motion2) os << "MOTION2: " << stats_debug_pretty(r.motion2->stats) << "\n";
+        if (r.vif) {
+            for (int k = 0; k < 4; ++k) os << "VIF_SCALE" << k << ": " << stats_debug_pretty(r.vif_scale[k]->stats) << "\n";
+            os << "VIF: " << stats_debug_pretty(r.vif->stats) << "\n";
+        }
         break;
     case Output::Json: { // serde_json::to_string_pretty: two-space indent, `"key": value`
         os << "{\n  \"frame_count\": " << r.frame_count;
@@ -132,6 +144,8 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
         put("psnr", r.psnr); put("ssim", r.ssim); put("msssim", r.msssim); put("ssimulacra2", r.ssimulacra2);
         put("xpsnr_y", r.xpsnr_y); put("xpsnr_u", r.xpsnr_u); put("xpsnr_v", r.xpsnr_v);
         put("motion", r.motion); put("motion2", r.motion2);
+        put("vif_scale0", r.vif_scale[0]); put("vif_scale1", r.vif_scale[1]); put("vif_scale2", r.vif_scale[2]); put("vif_scale3", r.vif_scale[3]);
+        put("vif", r.vif);
         os << "\n}\n";
         break;
     }
@@ -148,14 +162,20 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
         put_x("xpsnr_y", r.xpsnr_y); put_x("xpsnr_u", r.xpsnr_u); put_x("xpsnr_v", r.xpsnr_v);
         if (r.motion) put("motion", r.motion->stats);
         if (r.motion2) put("motion2", r.motion2->stats);
+        if (r.vif) {
+            static const char *const names[4] = {"vif_scale0", "vif_scale1", "vif_scale2", "vif_scale3"};
+            for (int k = 0; k < 4; ++k) put(names[k], r.vif_scale[k]->stats);
+            put("vif", r.vif->stats);
+        }
         os << "}\n";
         break;
     }
     case Output::CSV:
-        csv_header((bool)r.psnr, (bool)r.ssim, (bool)r.msssim, (bool)r.ssimulacra2, os, (bool)r.xpsnr_y, (bool)r.motion);
+        csv_header((bool)r.psnr, (bool)r.ssim, (bool)r.msssim, (bool)r.ssimulacra2, os, (bool)r.xpsnr_y, (bool)r.motion, (bool)r.vif);
         for (size_t i = 0; i < r.frame_count; ++i) {
             auto at = [&](const std::optional<MetricAggregate> &a) { return a ? std::optional<double>(a->scores[i]) : std::nullopt; };
-            csv_row(at(r.psnr), at(r.ssim), at(r.msssim), at(r.ssimulacra2), os, at(r.xpsnr_y), at(r.xpsnr_u), at(r.xpsnr_v), at(r.motion), at(r.motion2));
+            const std::optional<double> v5[5] = {at(r.vif_scale[0]), at(r.vif_scale[1]), at(r.vif_scale[2]), at(r.vif_scale[3]), at(r.vif)};
+            csv_row(at(r.psnr), at(r.ssim), at(r.msssim), at(r.ssimulacra2), os, at(r.xpsnr_y), at(r.xpsnr_u), at(r.xpsnr_v), at(r.motion), at(r.motion2), v5);
         }
         break;
     }

@@ -3,6 +3,7 @@
 #include "turbo_metrics.hpp"
 #include "../../include/turbo_metrics_xpsnr.h"
 #include "../../include/turbo_metrics_motion.h"
+#include "../../include/turbo_metrics_vif.h"
 #include <dlfcn.h>
 #include <array>
 #include <cmath>
@@ -355,6 +356,94 @@ struct MotionRun {
     }
 };
 
+// ---- VIF -----------------------------------------------------------------------------------------------------------
+// libturbometrics_vif.so, loaded at run time like the XPSNR and motion libraries (a CLI run without -m vif never loads it).  The lumas
+// of every kept pair are handed over as TM_MEM_HOST copies and computed batch by batch in stream order; a pair's five scores wait in
+// `ready` until the engine's scores of the same pair are drained.  No history: --every is fine.
+struct VifRun {
+    void *lib = nullptr;
+    int (*create)(tm_vif **, uint32_t, uint32_t, int, uint32_t, uint32_t) = nullptr;
+    void (*destroy)(tm_vif *) = nullptr;
+    int (*set_pair)(tm_vif *, uint32_t, const void *, const void *, size_t, size_t, int) = nullptr;
+    int (*compute_async)(tm_vif *, uint32_t) = nullptr;
+    int (*sync)(tm_vif *) = nullptr;
+    int (*get)(tm_vif *, uint32_t, uint32_t, tm_vif_frame *) = nullptr;
+    void (*scores)(const tm_vif_frame *, double *) = nullptr;
+    tm_vif *v = nullptr;
+    uint32_t w, h, batch;
+    int layout = -1;
+    uint32_t bits = 8, filled = 0;
+    std::deque<std::array<double, 5>> ready;
+
+    VifRun(uint32_t w_, uint32_t h_, uint32_t batch_) : w(w_), h(h_), batch(batch_)
+    {
+        const char *path = getenv("TM_VIF_LIB");
+        lib = dlopen(path ? path : "libturbometrics_vif.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("-m vif needs libturbometrics_vif.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_vif_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_vif_destroy");
+        set_pair = (decltype(set_pair))dlsym(lib, "tm_vif_set_pair");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_vif_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_vif_sync");
+        get = (decltype(get))dlsym(lib, "tm_vif_get");
+        scores = (decltype(scores))dlsym(lib, "tm_vif_scores");
+        if (!create || !destroy || !set_pair || !compute_async || !sync || !get || !scores)
+            throw std::runtime_error("libturbometrics_vif.so does not export include/turbo_metrics_vif.h");
+    }
+    ~VifRun()
+    {
+        if (v) destroy(v);
+        if (lib) dlclose(lib);
+    }
+    static void layout_of(const HwFrame &f, int &l, uint32_t &b)
+    {
+        switch (f.kind) {
+        case HwFrame::NvDecNV12: l = TM_VIF_Y8; b = 8; return;
+        case HwFrame::NvDecP016: l = TM_VIF_Y16_MSB; b = 10; return;
+        case HwFrame::Planar420: b = (uint32_t)f.bits; l = b == 8 ? TM_VIF_Y8 : TM_VIF_Y16_LOW; return;
+        case HwFrame::Planar420P10: l = TM_VIF_Y10_PACKED; b = 10; return;
+        default: throw std::runtime_error("vif needs YUV input (Y4M, raw planar YUV or decoded video), not RGB images");
+        }
+    }
+    void push(const HwFrame &r, const HwFrame &d)
+    {
+        int lr, ld;
+        uint32_t br, bd;
+        layout_of(r, lr, br);
+        layout_of(d, ld, bd);
+        if (lr != ld || br != bd || r.device != d.device) throw std::runtime_error("vif needs reference and distorted in the same YUV layout and bit depth");
+        if (!v) {
+            layout = lr; bits = br;
+            chk(create(&v, w, h, layout, bits, batch), "tm_vif_create");
+        } else if (lr != layout || br != bits) {
+            throw std::runtime_error("vif: the YUV layout changed inside the stream");
+        }
+        chk(set_pair(v, filled, r.data, d.data, r.pitch, d.pitch, r.device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_vif_set_pair");
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(v, filled), "tm_vif_compute_async");
+        chk(sync(v), "tm_vif_sync");
+        std::vector<tm_vif_frame> out(filled);
+        chk(get(v, 0, filled, out.data()), "tm_vif_get");
+        for (const tm_vif_frame &f : out) {
+            std::array<double, 5> s;
+            scores(&f, s.data());
+            ready.push_back(s);
+        }
+        filled = 0;
+    }
+    std::array<double, 5> pop()
+    {
+        if (ready.empty()) throw std::logic_error("vif: a pair's result is missing");
+        const std::array<double, 5> s = ready.front();
+        ready.pop_front();
+        return s;
+    }
+};
+
 void TurboMetrics::set_xpsnr_fps(uint32_t num, uint32_t den)
 {
     if (!xp_) throw std::runtime_error("xpsnr was not selected");
@@ -369,7 +458,8 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
 {
     if (metrics_.xpsnr) xp_ = std::make_unique<XpsnrRun>(w_, h_, batch_);
     if (metrics_.motion) mo_ = std::make_unique<MotionRun>(w_, h_, batch_);
-    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion)) return; // -m xpsnr or --motion alone: no SSIMULACRA2 / PSNR engine at all
+    if (metrics_.vif) vf_ = std::make_unique<VifRun>(w_, h_, batch_);
+    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif)) return; // -m xpsnr, -m vif or --motion alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -648,6 +738,9 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     // --motion: motion2 of a pair needs the next pair's motion, so a pair's row is held until the next one is drained (or the stream ends)
     std::optional<std::vector<double>> s_mo, s_mo2;
     if (mo_) { s_mo.emplace(); s_mo2.emplace(); }
+    std::optional<std::vector<double>> s_vf[5];
+    if (vf_)
+        for (auto &v : s_vf) v.emplace();
     std::optional<FrameScores> held;
     auto emit = [&](const FrameScores &r) {
         if (on_frame) on_frame(r);
@@ -668,6 +761,12 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
                 r.xpsnr_y = v[0]; r.xpsnr_u = v[1]; r.xpsnr_v = v[2];
                 for (int c = 0; c < 3; ++c) s_xp[c]->push_back(v[c]);
             }
+            if (vf_) {
+                const std::array<double, 5> v = vf_->pop();
+                for (int k = 0; k < 4; ++k) r.vif_scale[k] = v[k];
+                r.vif = v[4];
+                for (int k = 0; k < 5; ++k) s_vf[k]->push_back(v[k]);
+            }
             if (mo_) {
                 r.motion = mo_->pop();
                 if (held) {
@@ -687,6 +786,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (eng_[i]) chk(tm_engine_compute_async(eng_[i], filled[i]), "tm_engine_compute_async");
         if (xp_) xp_->flush();
         if (mo_) mo_->flush();
+        if (vf_) vf_->flush();
         in_flight[i] = true;
     };
 
@@ -755,6 +855,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         t0 = tick();
         if (xp_) xp_->push(fref, fdis);
         if (mo_) mo_->push(fref);
+        if (vf_) vf_->push(fref, fdis);
         if (eng_[cur]) {
             set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
             set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
@@ -793,7 +894,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_))
         throw NoFramesSelected();
     if (xp_) {
         std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
@@ -805,6 +906,10 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     if (s_mo) {
         res.motion = MetricAggregate::from(std::move(*s_mo));
         res.motion2 = MetricAggregate::from(std::move(*s_mo2));
+    }
+    if (vf_) {
+        for (int k = 0; k < 4; ++k) res.vif_scale[k] = MetricAggregate::from(std::move(*s_vf[k]));
+        res.vif = MetricAggregate::from(std::move(*s_vf[4]));
     }
     if (s_psnr) res.psnr = MetricAggregate::from(std::move(*s_psnr));
     if (s_ssim) res.ssim = MetricAggregate::from(std::move(*s_ssim));

@@ -33,6 +33,8 @@ struct Metrics {
     bool xpsnr = false;
     // VMAF's integer motion of the REFERENCE stream (include/turbo_metrics_motion.h, libturbometrics_motion.so): the CLI's --motion
     bool motion = false;
+    // VMAF's VIF of every pair's lumas (include/turbo_metrics_vif.h, libturbometrics_vif.so): the CLI's -m vif; not an engine metric
+    bool vif = false;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -66,6 +68,7 @@ struct MetricsResults {
     std::optional<MetricAggregate> psnr, ssim, msssim, ssimulacra2;
     std::optional<MetricAggregate> xpsnr_y, xpsnr_u, xpsnr_v;
     std::optional<MetricAggregate> motion, motion2; // their means are the sequence scores
+    std::optional<MetricAggregate> vif_scale[4], vif; // likewise
 };
 
 struct MetricsStats {
@@ -87,6 +90,7 @@ struct FrameScores {
     std::optional<double> psnr, ssim, msssim, ssimulacra2;
     std::optional<double> xpsnr_y, xpsnr_u, xpsnr_v;
     std::optional<double> motion, motion2;
+    std::optional<double> vif_scale[4], vif;
 };
 
 // ---- colour metadata (H.273 code points the reference understands, codec-bitstream/src/lib.rs:98-248) ----------
@@ -276,6 +280,7 @@ private:
     std::vector<std::pair<uint64_t, FrameScores>> def_done_;
     uint64_t def_next_ = 1;
     std::unique_ptr<struct XpsnrRun> xp_;                     // metrics_.xpsnr: the sequence's XPSNR state (library created at the first pair)
+    std::unique_ptr<struct VifRun> vf_;                       // metrics_.vif: the VIF library's state (likewise; no history)
     std::unique_ptr<struct MotionRun> mo_;                    // metrics_.motion: the reference stream's motion state (likewise)
     bool full_sums_ = false;                                  // settings replayed on an engine that is created later
     std::vector<std::pair<int, long long>> debug_params_;
