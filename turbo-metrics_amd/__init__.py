@@ -7,6 +7,7 @@ C ABI) with a host-side mirror of the reference's operator interface.
   xpsnr   -- ctypes binding of include/turbo_metrics_xpsnr.h (libturbometrics_xpsnr.so): Xpsnr, XPSNR of 4:2:0 sequences
   motion  -- ctypes binding of include/turbo_metrics_motion.h (libturbometrics_motion.so): Motion, VMAF's integer motion of a sequence
   vif     -- ctypes binding of include/turbo_metrics_vif.h (libturbometrics_vif.so): Vif, VMAF's VIF feature of frame pairs
+  adm     -- ctypes binding of include/turbo_metrics_adm.h (libturbometrics_adm.so): Adm, VMAF's ADM feature of frame pairs
 
 There is no CPU implementation in this package: without the HIP library (or without a gfx950 GPU)
 the operators raise.
@@ -18,3 +19,5 @@ from .xpsnr import Xpsnr, XpsnrFrame  # noqa: F401,E402
 from .motion import Motion, MotionFrame  # noqa: F401,E402
 from . import vif  # noqa: F401,E402
 from .vif import Vif, VifFrame  # noqa: F401,E402
+from . import adm  # noqa: F401,E402
+from .adm import Adm, AdmFrame  # noqa: F401,E402

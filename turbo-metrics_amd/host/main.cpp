@@ -48,6 +48,7 @@ void usage(std::ostream &os)
           "Options:\n"
           "  -m, --metrics <METRICS>    Select the metrics to compute [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr]\n"
           "                             and vif: VMAF's VIF of the luma planes, four scales (YUV inputs; runs beside the others or alone)\n"
+          "                             and adm: VMAF's ADM of the luma planes, adm2 and four scales (likewise)\n"
           "      --every <EVERY>        Only compute metrics every few frames [default: 0]\n"
           "      --skip <SKIP>          Index of the first frame to start computing at [default: 0]\n"
           "      --skip-ref <SKIP_REF>  Index of the first reference frame, additive with `skip` [default: 0]\n"
@@ -167,6 +168,7 @@ int main(int argc, char **argv)
             else if (s == "ssimulacra2") metrics.ssimulacra2 = true;
             else if (s == "xpsnr") metrics.xpsnr = true;
             else if (s == "vif") metrics.vif = true;
+            else if (s == "adm") metrics.adm = true;
             else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2]");
         } else if (a.rfind("-m", 0) == 0 && a.size() > 2 && a[1] == 'm') { // -mpsnr
             const std::string s = a.substr(2);
@@ -174,6 +176,7 @@ int main(int argc, char **argv)
             else if (s == "ssimulacra2") metrics.ssimulacra2 = true;
             else if (s == "xpsnr") metrics.xpsnr = true;
             else if (s == "vif") metrics.vif = true;
+            else if (s == "adm") metrics.adm = true;
             else return bad("invalid value '" + s + "' for '--metrics <METRICS>'");
         } else if (a == "--every") { if (!u32(opts.every)) return bad("invalid value for '--every <EVERY>'"); }
         else if (a == "--skip") { if (!u32(opts.skip)) return bad("invalid value for '--skip <SKIP>'"); }
@@ -232,6 +235,11 @@ int main(int argc, char **argv)
     if (metrics.vif) { // VIF runs on one device in the batched loop; sharding it is a later change
         const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
         if (why) { log_line(L_ERROR, kTarget, std::string("-m vif does not run with ") + why); return EXIT_FAILURE; }
+    }
+
+    if (metrics.adm) { // ADM, like VIF, runs on one device in the batched loop
+        const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
+        if (why) { log_line(L_ERROR, kTarget, std::string("-m adm does not run with ") + why); return EXIT_FAILURE; }
     }
 
     if (metrics.motion) { // motion compares consecutive pictures of ONE sequence on one device
@@ -487,7 +495,7 @@ int main(int argc, char **argv)
 
     std::unique_ptr<TurboMetrics> turbo;
     try {
-        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
+        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
         // a source that knows its length never needs more slots than it has pairs (a single image pair: one slot, one engine)
         const size_t known = std::min(source_ref->frame_count(), source_dis->frame_count());
         if (batch == 0) batch = auto_batch(source_ref->width(), source_ref->height());

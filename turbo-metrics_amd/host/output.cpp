@@ -28,7 +28,7 @@ std::vector<Named> stat_fields(const Stats &s)
             {"sample_stddev", s.sample_stddev}, {"p1", s.p1}, {"p5", s.p5}, {"p50", s.p50}, {"p95", s.p95}, {"p99", s.p99}};
 }
 
-void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os, bool xpsnr = false, bool motion = false, bool vif = false)
+void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os, bool xpsnr = false, bool motion = false, bool vif = false, bool adm = false)
 {
     bool first = true;
     auto put = [&](bool on, const char *n) { if (on) { os << (first ? "" : ",") << n; first = false; } };
@@ -36,6 +36,7 @@ void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os,
     put(xpsnr, "xpsnr_y"); put(xpsnr, "xpsnr_u"); put(xpsnr, "xpsnr_v");
     put(motion, "motion"); put(motion, "motion2");
     put(vif, "vif_scale0"); put(vif, "vif_scale1"); put(vif, "vif_scale2"); put(vif, "vif_scale3"); put(vif, "vif");
+    put(adm, "adm2"); put(adm, "adm_scale0"); put(adm, "adm_scale1"); put(adm, "adm_scale2"); put(adm, "adm_scale3");
     if (first) os << "\"\""; // csv::Writer writes an empty record as ""
     os << "\n";
 }
@@ -43,13 +44,16 @@ void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os,
 void csv_row(const std::optional<double> &a, const std::optional<double> &b, const std::optional<double> &c, const std::optional<double> &d,
              std::ostream &os, const std::optional<double> &xy = std::nullopt, const std::optional<double> &xu = std::nullopt,
              const std::optional<double> &xv = std::nullopt, const std::optional<double> &mo = std::nullopt,
-             const std::optional<double> &mo2 = std::nullopt, const std::optional<double> *vif5 = nullptr)
+             const std::optional<double> &mo2 = std::nullopt, const std::optional<double> *vif5 = nullptr,
+             const std::optional<double> *adm5 = nullptr)
 {
     bool first = true;
     auto put = [&](const std::optional<double> &v) { if (v) { os << (first ? "" : ",") << display(*v); first = false; } };
     put(a); put(b); put(c); put(d); put(xy); put(xu); put(xv); put(mo); put(mo2);
     if (vif5)
         for (int k = 0; k < 5; ++k) put(vif5[k]);
+    if (adm5)
+        for (int k = 0; k < 5; ++k) put(adm5[k]);
     if (first) os << "\"\"";
     os << "\n";
 }
@@ -68,6 +72,8 @@ std::string frame_scores_json(const FrameScores &r)
     put("motion", r.motion); put("motion2", r.motion2);
     put("vif_scale0", r.vif_scale[0]); put("vif_scale1", r.vif_scale[1]); put("vif_scale2", r.vif_scale[2]); put("vif_scale3", r.vif_scale[3]);
     put("vif", r.vif);
+    put("adm2", r.adm2);
+    put("adm_scale0", r.adm_scale[0]); put("adm_scale1", r.adm_scale[1]); put("adm_scale2", r.adm_scale[2]); put("adm_scale3", r.adm_scale[3]);
     return s + "}";
 }
 
@@ -97,7 +103,7 @@ std::string stats_json(const Stats &s, int indent, bool pretty)
 
 void output_prepare(Output o, const Metrics &m, std::ostream &os)
 {
-    if (o == Output::CSV) csv_header(m.psnr, m.ssim, m.msssim, m.ssimulacra2, os, m.xpsnr, m.motion, m.vif);
+    if (o == Output::CSV) csv_header(m.psnr, m.ssim, m.msssim, m.ssimulacra2, os, m.xpsnr, m.motion, m.vif, m.adm);
 }
 
 void output_single_score(Output o, const FrameScores &r, std::ostream &os)
@@ -105,7 +111,8 @@ void output_single_score(Output o, const FrameScores &r, std::ostream &os)
     if (o == Output::JsonLines) os << frame_scores_json(r) << "\n";
     else if (o == Output::CSV) {
         const std::optional<double> v5[5] = {r.vif_scale[0], r.vif_scale[1], r.vif_scale[2], r.vif_scale[3], r.vif};
-        csv_row(r.psnr, r.ssim, r.msssim, r.ssimulacra2, os, r.xpsnr_y, r.xpsnr_u, r.xpsnr_v, r.motion, r.motion2, v5);
+        const std::optional<double> a5[5] = {r.adm2, r.adm_scale[0], r.adm_scale[1], r.adm_scale[2], r.adm_scale[3]};
+        csv_row(r.psnr, r.ssim, r.msssim, r.ssimulacra2, os, r.xpsnr_y, r.xpsnr_u, r.xpsnr_v, r.motion, r.motion2, v5, a5);
     }
 }
 
@@ -130,6 +137,10 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
             for (int k = 0; k < 4; ++k) os << "VIF_SCALE" << k << ": " << stats_debug_pretty(r.vif_scale[k]->stats) << "\n";
             os << "VIF: " << stats_debug_pretty(r.vif->stats) << "\n";
         }
+        if (r.adm2) {
+            os << "ADM2: " << stats_debug_pretty(r.adm2->stats) << "\n";
+            for (int k = 0; k < 4; ++k) os << "ADM_SCALE" << k << ": " << stats_debug_pretty(r.adm_scale[k]->stats) << "\n";
+        }
         break;
     case Output::Json: { // serde_json::to_string_pretty: two-space indent, `"key": value`
         os << "{\n  \"frame_count\": " << r.frame_count;
@@ -146,6 +157,8 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
         put("motion", r.motion); put("motion2", r.motion2);
         put("vif_scale0", r.vif_scale[0]); put("vif_scale1", r.vif_scale[1]); put("vif_scale2", r.vif_scale[2]); put("vif_scale3", r.vif_scale[3]);
         put("vif", r.vif);
+        put("adm2", r.adm2);
+        put("adm_scale0", r.adm_scale[0]); put("adm_scale1", r.adm_scale[1]); put("adm_scale2", r.adm_scale[2]); put("adm_scale3", r.adm_scale[3]);
         os << "\n}\n";
         break;
     }
@@ -167,15 +180,21 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
             for (int k = 0; k < 4; ++k) put(names[k], r.vif_scale[k]->stats);
             put("vif", r.vif->stats);
         }
+        if (r.adm2) {
+            static const char *const names[4] = {"adm_scale0", "adm_scale1", "adm_scale2", "adm_scale3"};
+            put("adm2", r.adm2->stats);
+            for (int k = 0; k < 4; ++k) put(names[k], r.adm_scale[k]->stats);
+        }
         os << "}\n";
         break;
     }
     case Output::CSV:
-        csv_header((bool)r.psnr, (bool)r.ssim, (bool)r.msssim, (bool)r.ssimulacra2, os, (bool)r.xpsnr_y, (bool)r.motion, (bool)r.vif);
+        csv_header((bool)r.psnr, (bool)r.ssim, (bool)r.msssim, (bool)r.ssimulacra2, os, (bool)r.xpsnr_y, (bool)r.motion, (bool)r.vif, (bool)r.adm2);
         for (size_t i = 0; i < r.frame_count; ++i) {
             auto at = [&](const std::optional<MetricAggregate> &a) { return a ? std::optional<double>(a->scores[i]) : std::nullopt; };
             const std::optional<double> v5[5] = {at(r.vif_scale[0]), at(r.vif_scale[1]), at(r.vif_scale[2]), at(r.vif_scale[3]), at(r.vif)};
-            csv_row(at(r.psnr), at(r.ssim), at(r.msssim), at(r.ssimulacra2), os, at(r.xpsnr_y), at(r.xpsnr_u), at(r.xpsnr_v), at(r.motion), at(r.motion2), v5);
+            const std::optional<double> a5[5] = {at(r.adm2), at(r.adm_scale[0]), at(r.adm_scale[1]), at(r.adm_scale[2]), at(r.adm_scale[3])};
+            csv_row(at(r.psnr), at(r.ssim), at(r.msssim), at(r.ssimulacra2), os, at(r.xpsnr_y), at(r.xpsnr_u), at(r.xpsnr_v), at(r.motion), at(r.motion2), v5, a5);
         }
         break;
     }

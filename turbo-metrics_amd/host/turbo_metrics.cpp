@@ -4,6 +4,7 @@
 #include "../../include/turbo_metrics_xpsnr.h"
 #include "../../include/turbo_metrics_motion.h"
 #include "../../include/turbo_metrics_vif.h"
+#include "../../include/turbo_metrics_adm.h"
 #include <dlfcn.h>
 #include <array>
 #include <cmath>
@@ -444,6 +445,94 @@ struct VifRun {
     }
 };
 
+// ---- ADM -----------------------------------------------------------------------------------------------------------
+// libturbometrics_adm.so, loaded at run time like the XPSNR, motion and VIF libraries (a CLI run without -m adm never loads it).  The
+// lumas of every kept pair are handed over as TM_MEM_HOST copies and computed batch by batch in stream order; a pair's five scores
+// (adm_scale0 .. adm_scale3, adm2) wait in `ready` until the engine's scores of the same pair are drained.  No history: --every is fine.
+struct AdmRun {
+    void *lib = nullptr;
+    int (*create)(tm_adm **, uint32_t, uint32_t, int, uint32_t, uint32_t) = nullptr;
+    void (*destroy)(tm_adm *) = nullptr;
+    int (*set_pair)(tm_adm *, uint32_t, const void *, const void *, size_t, size_t, int) = nullptr;
+    int (*compute_async)(tm_adm *, uint32_t) = nullptr;
+    int (*sync)(tm_adm *) = nullptr;
+    int (*get)(tm_adm *, uint32_t, uint32_t, tm_adm_frame *) = nullptr;
+    void (*scores)(const tm_adm_frame *, uint32_t, uint32_t, double *) = nullptr;
+    tm_adm *v = nullptr;
+    uint32_t w, h, batch;
+    int layout = -1;
+    uint32_t bits = 8, filled = 0;
+    std::deque<std::array<double, 5>> ready;
+
+    AdmRun(uint32_t w_, uint32_t h_, uint32_t batch_) : w(w_), h(h_), batch(batch_)
+    {
+        const char *path = getenv("TM_ADM_LIB");
+        lib = dlopen(path ? path : "libturbometrics_adm.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("-m adm needs libturbometrics_adm.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_adm_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_adm_destroy");
+        set_pair = (decltype(set_pair))dlsym(lib, "tm_adm_set_pair");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_adm_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_adm_sync");
+        get = (decltype(get))dlsym(lib, "tm_adm_get");
+        scores = (decltype(scores))dlsym(lib, "tm_adm_scores");
+        if (!create || !destroy || !set_pair || !compute_async || !sync || !get || !scores)
+            throw std::runtime_error("libturbometrics_adm.so does not export include/turbo_metrics_adm.h");
+    }
+    ~AdmRun()
+    {
+        if (v) destroy(v);
+        if (lib) dlclose(lib);
+    }
+    static void layout_of(const HwFrame &f, int &l, uint32_t &b)
+    {
+        switch (f.kind) {
+        case HwFrame::NvDecNV12: l = TM_ADM_Y8; b = 8; return;
+        case HwFrame::NvDecP016: l = TM_ADM_Y16_MSB; b = 10; return;
+        case HwFrame::Planar420: b = (uint32_t)f.bits; l = b == 8 ? TM_ADM_Y8 : TM_ADM_Y16_LOW; return;
+        case HwFrame::Planar420P10: l = TM_ADM_Y10_PACKED; b = 10; return;
+        default: throw std::runtime_error("adm needs YUV input (Y4M, raw planar YUV or decoded video), not RGB images");
+        }
+    }
+    void push(const HwFrame &r, const HwFrame &d)
+    {
+        int lr, ld;
+        uint32_t br, bd;
+        layout_of(r, lr, br);
+        layout_of(d, ld, bd);
+        if (lr != ld || br != bd || r.device != d.device) throw std::runtime_error("adm needs reference and distorted in the same YUV layout and bit depth");
+        if (!v) {
+            layout = lr; bits = br;
+            chk(create(&v, w, h, layout, bits, batch), "tm_adm_create");
+        } else if (lr != layout || br != bits) {
+            throw std::runtime_error("adm: the YUV layout changed inside the stream");
+        }
+        chk(set_pair(v, filled, r.data, d.data, r.pitch, d.pitch, r.device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_adm_set_pair");
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(v, filled), "tm_adm_compute_async");
+        chk(sync(v), "tm_adm_sync");
+        std::vector<tm_adm_frame> out(filled);
+        chk(get(v, 0, filled, out.data()), "tm_adm_get");
+        for (const tm_adm_frame &f : out) {
+            std::array<double, 5> s;
+            scores(&f, w, h, s.data());
+            ready.push_back(s);
+        }
+        filled = 0;
+    }
+    std::array<double, 5> pop()
+    {
+        if (ready.empty()) throw std::logic_error("adm: a pair's result is missing");
+        const std::array<double, 5> s = ready.front();
+        ready.pop_front();
+        return s;
+    }
+};
+
 void TurboMetrics::set_xpsnr_fps(uint32_t num, uint32_t den)
 {
     if (!xp_) throw std::runtime_error("xpsnr was not selected");
@@ -459,7 +548,8 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
     if (metrics_.xpsnr) xp_ = std::make_unique<XpsnrRun>(w_, h_, batch_);
     if (metrics_.motion) mo_ = std::make_unique<MotionRun>(w_, h_, batch_);
     if (metrics_.vif) vf_ = std::make_unique<VifRun>(w_, h_, batch_);
-    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif)) return; // -m xpsnr, -m vif or --motion alone: no SSIMULACRA2 / PSNR engine at all
+    if (metrics_.adm) ad_ = std::make_unique<AdmRun>(w_, h_, batch_);
+    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm)) return; // -m xpsnr, -m vif, -m adm or --motion alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -741,6 +831,9 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     std::optional<std::vector<double>> s_vf[5];
     if (vf_)
         for (auto &v : s_vf) v.emplace();
+    std::optional<std::vector<double>> s_ad[5]; // adm_scale0 .. adm_scale3, adm2
+    if (ad_)
+        for (auto &v : s_ad) v.emplace();
     std::optional<FrameScores> held;
     auto emit = [&](const FrameScores &r) {
         if (on_frame) on_frame(r);
@@ -767,6 +860,12 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
                 r.vif = v[4];
                 for (int k = 0; k < 5; ++k) s_vf[k]->push_back(v[k]);
             }
+            if (ad_) {
+                const std::array<double, 5> v = ad_->pop();
+                for (int k = 0; k < 4; ++k) r.adm_scale[k] = v[k];
+                r.adm2 = v[4];
+                for (int k = 0; k < 5; ++k) s_ad[k]->push_back(v[k]);
+            }
             if (mo_) {
                 r.motion = mo_->pop();
                 if (held) {
@@ -787,6 +886,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (xp_) xp_->flush();
         if (mo_) mo_->flush();
         if (vf_) vf_->flush();
+        if (ad_) ad_->flush();
         in_flight[i] = true;
     };
 
@@ -856,6 +956,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (xp_) xp_->push(fref, fdis);
         if (mo_) mo_->push(fref);
         if (vf_) vf_->push(fref, fdis);
+        if (ad_) ad_->push(fref, fdis);
         if (eng_[cur]) {
             set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
             set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
@@ -894,7 +995,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_))
         throw NoFramesSelected();
     if (xp_) {
         std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
@@ -910,6 +1011,10 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     if (vf_) {
         for (int k = 0; k < 4; ++k) res.vif_scale[k] = MetricAggregate::from(std::move(*s_vf[k]));
         res.vif = MetricAggregate::from(std::move(*s_vf[4]));
+    }
+    if (ad_) {
+        for (int k = 0; k < 4; ++k) res.adm_scale[k] = MetricAggregate::from(std::move(*s_ad[k]));
+        res.adm2 = MetricAggregate::from(std::move(*s_ad[4]));
     }
     if (s_psnr) res.psnr = MetricAggregate::from(std::move(*s_psnr));
     if (s_ssim) res.ssim = MetricAggregate::from(std::move(*s_ssim));

@@ -35,6 +35,8 @@ struct Metrics {
     bool motion = false;
     // VMAF's VIF of every pair's lumas (include/turbo_metrics_vif.h, libturbometrics_vif.so): the CLI's -m vif; not an engine metric
     bool vif = false;
+    // VMAF's ADM of every pair's lumas (include/turbo_metrics_adm.h, libturbometrics_adm.so): the CLI's -m adm; not an engine metric
+    bool adm = false;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -69,6 +71,7 @@ struct MetricsResults {
     std::optional<MetricAggregate> xpsnr_y, xpsnr_u, xpsnr_v;
     std::optional<MetricAggregate> motion, motion2; // their means are the sequence scores
     std::optional<MetricAggregate> vif_scale[4], vif; // likewise
+    std::optional<MetricAggregate> adm2, adm_scale[4]; // likewise
 };
 
 struct MetricsStats {
@@ -91,6 +94,7 @@ struct FrameScores {
     std::optional<double> xpsnr_y, xpsnr_u, xpsnr_v;
     std::optional<double> motion, motion2;
     std::optional<double> vif_scale[4], vif;
+    std::optional<double> adm2, adm_scale[4];
 };
 
 // ---- colour metadata (H.273 code points the reference understands, codec-bitstream/src/lib.rs:98-248) ----------
@@ -281,6 +285,7 @@ private:
     uint64_t def_next_ = 1;
     std::unique_ptr<struct XpsnrRun> xp_;                     // metrics_.xpsnr: the sequence's XPSNR state (library created at the first pair)
     std::unique_ptr<struct VifRun> vf_;                       // metrics_.vif: the VIF library's state (likewise; no history)
+    std::unique_ptr<struct AdmRun> ad_;                       // metrics_.adm: the ADM library's state (likewise; no history)
     std::unique_ptr<struct MotionRun> mo_;                    // metrics_.motion: the reference stream's motion state (likewise)
     bool full_sums_ = false;                                  // settings replayed on an engine that is created later
     std::vector<std::pair<int, long long>> debug_params_;
