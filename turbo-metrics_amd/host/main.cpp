@@ -69,6 +69,10 @@ void usage(std::ostream &os)
           "      --color-primaries <N> --matrix-coefficients <N> --transfer-characteristics <N>   H.273 codes (1, 5, 6; 2 = by height)\n"
           "      --full-range           the YUV input is full range (unsupported by the reference and here)\n"
           "      --motion               also compute VMAF's integer motion / motion2 of the REFERENCE stream (YUV inputs; runs beside -m or alone)\n"
+          "      --scenes               also find the scene cuts of the REFERENCE stream from luma histograms: per-frame scene_score and scene_cut,\n"
+          "                             and scene_starts, the frames at which a scene begins (YUV inputs; runs beside -m or alone)\n"
+          "      --scene-threshold <X>  a frame whose scene_score reaches X starts a scene, 0 < X <= 1 (with --scenes) [default: 0.5]\n"
+          "      --scene-bins <N>       histogram bins the score compares, after merging neighbours: 8, 16, 32, 64, 128 or 256 (with --scenes) [default: 64]\n"
           "      --xpsnr-fps <N[/D]>    frame rate that picks XPSNR's temporal order (below 32: first order) [default: the Y4M F token, else 25]\n"
           "  -h, --help                 Print help\n"
           "  -V, --version              Print version\n";
@@ -134,7 +138,7 @@ int main(int argc, char **argv)
     SourceHints hints;
     uint32_t batch = 0 /* 0: chosen from the picture size */, device = 0, devices = 1, ranks = 0 /* 0: not asked for */, in_flight_pairs = 2;
     uint32_t xpsnr_fps_num = 0, xpsnr_fps_den = 1; // --xpsnr-fps (0: not given)
-    bool pipeline = true, full_sums = false, in_flight_given = false;
+    bool pipeline = true, full_sums = false, in_flight_given = false, scene_values_given = false;
     enum class Loop { Batched, Reference, Deferred } loop = Loop::Batched;
     std::vector<std::pair<int, long long>> tune;
 
@@ -200,6 +204,25 @@ int main(int argc, char **argv)
         }
         else if (a == "--full-sums") full_sums = true;
         else if (a == "--motion") metrics.motion = true;
+        else if (a == "--scenes") metrics.scenes = true;
+        else if (a == "--scene-threshold") {
+            std::string v;
+            if (!value(v)) return bad("a value is required for '--scene-threshold <X>' but none was supplied");
+            char *end = nullptr;
+            const double x = strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(x > 0.0 && x <= 1.0)) return bad("invalid value '" + v + "' for '--scene-threshold <X>'\n  [0 < X <= 1]");
+            metrics.scene_threshold = x;
+            scene_values_given = true;
+        }
+        else if (a == "--scene-bins") {
+            std::string v;
+            if (!value(v)) return bad("a value is required for '--scene-bins <N>' but none was supplied");
+            uint32_t n = 0;
+            if (!parse_u32(v, n) || (n != 8 && n != 16 && n != 32 && n != 64 && n != 128 && n != 256))
+                return bad("invalid value '" + v + "' for '--scene-bins <N>'\n  [possible values: 8, 16, 32, 64, 128, 256]");
+            metrics.scene_bins = n;
+            scene_values_given = true;
+        }
         else if (a == "--xpsnr-fps") {
             std::string v;
             if (!value(v)) return bad("a value is required for '--xpsnr-fps <N[/D]>'");
@@ -224,6 +247,14 @@ int main(int argc, char **argv)
         else pos.push_back(a);
     }
     if (pos.size() != 2) return bad("the following required arguments were not provided:\n  <REFERENCE>\n  <DISTORTED>");
+    if (scene_values_given && !metrics.scenes) return bad("'--scene-threshold <X>' and '--scene-bins <N>' belong to '--scenes'");
+    if (metrics.scenes) { // a frame is compared with the frame before it in ONE stream on one device
+        const char *why = devices != 1 ? "--devices (shards would cut the sequence)"
+                        : ranks > 0 ? "--ranks (shards would cut the sequence)"
+                        : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
+        if (why) { log_line(L_ERROR, kTarget, std::string("--scenes does not run with ") + why); return EXIT_FAILURE; }
+    }
+
     if (metrics.xpsnr) { // XPSNR is stateful across the frames of ONE sequence on one device
         const char *why = opts.every > 1 ? "--every > 1 (skipped pictures never reach its temporal history)"
                         : devices != 1 ? "--devices (shards would cut its temporal history)"
@@ -495,7 +526,7 @@ int main(int argc, char **argv)
 
     std::unique_ptr<TurboMetrics> turbo;
     try {
-        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
+        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
         // a source that knows its length never needs more slots than it has pairs (a single image pair: one slot, one engine)
         const size_t known = std::min(source_ref->frame_count(), source_dis->frame_count());
         if (batch == 0) batch = auto_batch(source_ref->width(), source_ref->height());

@@ -28,7 +28,8 @@ std::vector<Named> stat_fields(const Stats &s)
             {"sample_stddev", s.sample_stddev}, {"p1", s.p1}, {"p5", s.p5}, {"p50", s.p50}, {"p95", s.p95}, {"p99", s.p99}};
 }
 
-void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os, bool xpsnr = false, bool motion = false, bool vif = false, bool adm = false)
+void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os, bool xpsnr = false, bool motion = false, bool vif = false, bool adm = false,
+                bool scene = false)
 {
     bool first = true;
     auto put = [&](bool on, const char *n) { if (on) { os << (first ? "" : ",") << n; first = false; } };
@@ -37,6 +38,7 @@ void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os,
     put(motion, "motion"); put(motion, "motion2");
     put(vif, "vif_scale0"); put(vif, "vif_scale1"); put(vif, "vif_scale2"); put(vif, "vif_scale3"); put(vif, "vif");
     put(adm, "adm2"); put(adm, "adm_scale0"); put(adm, "adm_scale1"); put(adm, "adm_scale2"); put(adm, "adm_scale3");
+    put(scene, "scene_score"); put(scene, "scene_cut");
     if (first) os << "\"\""; // csv::Writer writes an empty record as ""
     os << "\n";
 }
@@ -45,7 +47,8 @@ void csv_row(const std::optional<double> &a, const std::optional<double> &b, con
              std::ostream &os, const std::optional<double> &xy = std::nullopt, const std::optional<double> &xu = std::nullopt,
              const std::optional<double> &xv = std::nullopt, const std::optional<double> &mo = std::nullopt,
              const std::optional<double> &mo2 = std::nullopt, const std::optional<double> *vif5 = nullptr,
-             const std::optional<double> *adm5 = nullptr)
+             const std::optional<double> *adm5 = nullptr, const std::optional<double> &scene_score = std::nullopt,
+             const std::optional<bool> &scene_cut = std::nullopt)
 {
     bool first = true;
     auto put = [&](const std::optional<double> &v) { if (v) { os << (first ? "" : ",") << display(*v); first = false; } };
@@ -54,8 +57,18 @@ void csv_row(const std::optional<double> &a, const std::optional<double> &b, con
         for (int k = 0; k < 5; ++k) put(vif5[k]);
     if (adm5)
         for (int k = 0; k < 5; ++k) put(adm5[k]);
+    put(scene_score);
+    if (scene_cut) { os << (first ? "" : ",") << (*scene_cut ? 1 : 0); first = false; } // a flag: 0 / 1, not a float
     if (first) os << "\"\"";
     os << "\n";
+}
+
+// [0, 4, 7]
+std::string index_list(const std::vector<size_t> &v, const char *sep)
+{
+    std::string s = "[";
+    for (size_t i = 0; i < v.size(); ++i) s += (i ? sep : "") + std::to_string(v[i]);
+    return s + "]";
 }
 
 std::string frame_scores_json(const FrameScores &r)
@@ -74,6 +87,8 @@ std::string frame_scores_json(const FrameScores &r)
     put("vif", r.vif);
     put("adm2", r.adm2);
     put("adm_scale0", r.adm_scale[0]); put("adm_scale1", r.adm_scale[1]); put("adm_scale2", r.adm_scale[2]); put("adm_scale3", r.adm_scale[3]);
+    put("scene_score", r.scene_score);
+    if (r.scene_cut) s += (first ? "\"" : ",\"") + std::string("scene_cut\":") + (*r.scene_cut ? "1" : "0");
     return s + "}";
 }
 
@@ -103,7 +118,7 @@ std::string stats_json(const Stats &s, int indent, bool pretty)
 
 void output_prepare(Output o, const Metrics &m, std::ostream &os)
 {
-    if (o == Output::CSV) csv_header(m.psnr, m.ssim, m.msssim, m.ssimulacra2, os, m.xpsnr, m.motion, m.vif, m.adm);
+    if (o == Output::CSV) csv_header(m.psnr, m.ssim, m.msssim, m.ssimulacra2, os, m.xpsnr, m.motion, m.vif, m.adm, m.scenes);
 }
 
 void output_single_score(Output o, const FrameScores &r, std::ostream &os)
@@ -112,7 +127,7 @@ void output_single_score(Output o, const FrameScores &r, std::ostream &os)
     else if (o == Output::CSV) {
         const std::optional<double> v5[5] = {r.vif_scale[0], r.vif_scale[1], r.vif_scale[2], r.vif_scale[3], r.vif};
         const std::optional<double> a5[5] = {r.adm2, r.adm_scale[0], r.adm_scale[1], r.adm_scale[2], r.adm_scale[3]};
-        csv_row(r.psnr, r.ssim, r.msssim, r.ssimulacra2, os, r.xpsnr_y, r.xpsnr_u, r.xpsnr_v, r.motion, r.motion2, v5, a5);
+        csv_row(r.psnr, r.ssim, r.msssim, r.ssimulacra2, os, r.xpsnr_y, r.xpsnr_u, r.xpsnr_v, r.motion, r.motion2, v5, a5, r.scene_score, r.scene_cut);
     }
 }
 
@@ -141,6 +156,10 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
             os << "ADM2: " << stats_debug_pretty(r.adm2->stats) << "\n";
             for (int k = 0; k < 4; ++k) os << "ADM_SCALE" << k << ": " << stats_debug_pretty(r.adm_scale[k]->stats) << "\n";
         }
+        if (r.scene_score) {
+            os << "SCENE_SCORE: " << stats_debug_pretty(r.scene_score->stats) << "\n";
+            os << "SCENE_STARTS: " << index_list(r.scene_starts, ", ") << "\n";
+        }
         break;
     case Output::Json: { // serde_json::to_string_pretty: two-space indent, `"key": value`
         os << "{\n  \"frame_count\": " << r.frame_count;
@@ -159,6 +178,8 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
         put("vif", r.vif);
         put("adm2", r.adm2);
         put("adm_scale0", r.adm_scale[0]); put("adm_scale1", r.adm_scale[1]); put("adm_scale2", r.adm_scale[2]); put("adm_scale3", r.adm_scale[3]);
+        put("scene_score", r.scene_score);
+        if (r.scene_score) os << ",\n  \"scene_starts\": " << index_list(r.scene_starts, ", ");
         os << "\n}\n";
         break;
     }
@@ -185,16 +206,22 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
             put("adm2", r.adm2->stats);
             for (int k = 0; k < 4; ++k) put(names[k], r.adm_scale[k]->stats);
         }
+        if (r.scene_score) {
+            put("scene_score", r.scene_score->stats);
+            os << ",\"scene_starts\":" << index_list(r.scene_starts, ",");
+        }
         os << "}\n";
         break;
     }
     case Output::CSV:
-        csv_header((bool)r.psnr, (bool)r.ssim, (bool)r.msssim, (bool)r.ssimulacra2, os, (bool)r.xpsnr_y, (bool)r.motion, (bool)r.vif, (bool)r.adm2);
-        for (size_t i = 0; i < r.frame_count; ++i) {
+        csv_header((bool)r.psnr, (bool)r.ssim, (bool)r.msssim, (bool)r.ssimulacra2, os, (bool)r.xpsnr_y, (bool)r.motion, (bool)r.vif, (bool)r.adm2, (bool)r.scene_score);
+        for (size_t i = 0, starts = 0; i < r.frame_count; ++i) {
             auto at = [&](const std::optional<MetricAggregate> &a) { return a ? std::optional<double>(a->scores[i]) : std::nullopt; };
             const std::optional<double> v5[5] = {at(r.vif_scale[0]), at(r.vif_scale[1]), at(r.vif_scale[2]), at(r.vif_scale[3]), at(r.vif)};
             const std::optional<double> a5[5] = {at(r.adm2), at(r.adm_scale[0]), at(r.adm_scale[1]), at(r.adm_scale[2]), at(r.adm_scale[3])};
-            csv_row(at(r.psnr), at(r.ssim), at(r.msssim), at(r.ssimulacra2), os, at(r.xpsnr_y), at(r.xpsnr_u), at(r.xpsnr_v), at(r.motion), at(r.motion2), v5, a5);
+            csv_row(at(r.psnr), at(r.ssim), at(r.msssim), at(r.ssimulacra2), os, at(r.xpsnr_y), at(r.xpsnr_u), at(r.xpsnr_v), at(r.motion), at(r.motion2), v5, a5,
+                    at(r.scene_score), r.scene_score ? std::optional<bool>(i > 0 && starts < r.scene_starts.size() && r.scene_starts[starts] == i) : std::nullopt);
+            if (starts < r.scene_starts.size() && r.scene_starts[starts] == i) ++starts; // (frame 0 starts the first scene and is no cut)
         }
         break;
     }

@@ -3,6 +3,7 @@
 #include "turbo_metrics.hpp"
 #include "../../include/turbo_metrics_xpsnr.h"
 #include "../../include/turbo_metrics_motion.h"
+#include "../../include/turbo_metrics_scene.h"
 #include "../../include/turbo_metrics_vif.h"
 #include "../../include/turbo_metrics_adm.h"
 #include <dlfcn.h>
@@ -357,6 +358,108 @@ struct MotionRun {
     }
 };
 
+// ---- scene cuts ------------------------------------------------------------------------------------------------------
+// libturbometrics_scene.so, loaded at run time like the motion library (a CLI run without --scenes never loads it).  The REFERENCE
+// luma of every kept pair is handed over as a TM_MEM_HOST copy and its histogram computed batch by batch in stream order; the
+// previous kept picture's histogram stays here, on the host, across batches.  The verdict is the library's host functions: nothing
+// here restates the definition.  A picture's {score, cut} waits in `ready` until the engine's scores of the same pair are drained.
+// No device history: --every is fine (the score is then that against the previous KEPT picture).
+struct SceneRun {
+    void *lib = nullptr;
+    int (*create)(tm_scene **, uint32_t, uint32_t, int, uint32_t, uint32_t) = nullptr;
+    void (*destroy)(tm_scene *) = nullptr;
+    int (*set_frame)(tm_scene *, uint32_t, const void *, size_t, int) = nullptr;
+    int (*compute_async)(tm_scene *, uint32_t) = nullptr;
+    int (*sync)(tm_scene *) = nullptr;
+    int (*get)(tm_scene *, uint32_t, uint32_t, tm_scene_frame *) = nullptr;
+    int (*distance)(const uint32_t *, const uint32_t *, int, uint64_t *) = nullptr;
+    double (*score)(uint64_t, uint32_t, uint32_t) = nullptr;
+    int (*is_cut)(double, double) = nullptr;
+    tm_scene *s = nullptr;
+    uint32_t w, h, batch;
+    int bins;
+    double threshold;
+    int layout = -1;
+    uint32_t bits = 8, filled = 0;
+    bool have_prev = false;
+    tm_scene_frame prev;
+    std::vector<tm_scene_frame> out;
+    std::deque<std::pair<double, bool>> ready;
+
+    SceneRun(uint32_t w_, uint32_t h_, uint32_t batch_, uint32_t bins_, double threshold_)
+        : w(w_), h(h_), batch(batch_), bins((int)bins_), threshold(threshold_)
+    {
+        const char *path = getenv("TM_SCENE_LIB");
+        lib = dlopen(path ? path : "libturbometrics_scene.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("--scenes needs libturbometrics_scene.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_scene_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_scene_destroy");
+        set_frame = (decltype(set_frame))dlsym(lib, "tm_scene_set_frame");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_scene_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_scene_sync");
+        get = (decltype(get))dlsym(lib, "tm_scene_get");
+        distance = (decltype(distance))dlsym(lib, "tm_scene_distance");
+        score = (decltype(score))dlsym(lib, "tm_scene_score");
+        is_cut = (decltype(is_cut))dlsym(lib, "tm_scene_is_cut");
+        if (!create || !destroy || !set_frame || !compute_async || !sync || !get || !distance || !score || !is_cut)
+            throw std::runtime_error("libturbometrics_scene.so does not export include/turbo_metrics_scene.h");
+    }
+    ~SceneRun()
+    {
+        if (s) destroy(s);
+        if (lib) dlclose(lib);
+    }
+    void push(const HwFrame &r)
+    {
+        int l;
+        uint32_t b;
+        switch (r.kind) {
+        case HwFrame::NvDecNV12: l = TM_SCENE_Y8; b = 8; break;
+        case HwFrame::NvDecP016: l = TM_SCENE_Y16_MSB; b = 10; break;
+        case HwFrame::Planar420: b = (uint32_t)r.bits; l = b == 8 ? TM_SCENE_Y8 : TM_SCENE_Y16_LOW; break;
+        case HwFrame::Planar420P10: l = TM_SCENE_Y10_PACKED; b = 10; break;
+        default: throw std::runtime_error("scenes needs YUV input (Y4M, raw planar YUV or decoded video), not RGB images");
+        }
+        if (!s) {
+            layout = l; bits = b;
+            chk(create(&s, w, h, layout, bits, batch), "tm_scene_create");
+        } else if (l != layout || b != bits) {
+            throw std::runtime_error("scenes: the YUV layout changed inside the stream");
+        }
+        chk(set_frame(s, filled, r.data, r.pitch, r.device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_scene_set_frame");
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(s, filled), "tm_scene_compute_async");
+        chk(sync(s), "tm_scene_sync");
+        out.resize(filled);
+        chk(get(s, 0, filled, out.data()), "tm_scene_get");
+        for (const tm_scene_frame &f : out) {
+            double sc = 0.0; // the first picture of a sequence has score 0 and is never a cut
+            bool cut = false;
+            if (have_prev) {
+                uint64_t d = 0;
+                chk(distance(prev.hist, f.hist, bins, &d), "tm_scene_distance");
+                sc = score(d, w, h);
+                cut = is_cut(sc, threshold) != 0;
+            }
+            ready.emplace_back(sc, cut);
+            prev = f;
+            have_prev = true;
+        }
+        filled = 0;
+    }
+    std::pair<double, bool> pop()
+    {
+        if (ready.empty()) throw std::logic_error("scenes: a picture's result is missing");
+        const std::pair<double, bool> v = ready.front();
+        ready.pop_front();
+        return v;
+    }
+};
+
 // ---- VIF -----------------------------------------------------------------------------------------------------------
 // libturbometrics_vif.so, loaded at run time like the XPSNR and motion libraries (a CLI run without -m vif never loads it).  The lumas
 // of every kept pair are handed over as TM_MEM_HOST copies and computed batch by batch in stream order; a pair's five scores wait in
@@ -549,7 +652,8 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
     if (metrics_.motion) mo_ = std::make_unique<MotionRun>(w_, h_, batch_);
     if (metrics_.vif) vf_ = std::make_unique<VifRun>(w_, h_, batch_);
     if (metrics_.adm) ad_ = std::make_unique<AdmRun>(w_, h_, batch_);
-    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm)) return; // -m xpsnr, -m vif, -m adm or --motion alone: no SSIMULACRA2 / PSNR engine at all
+    if (metrics_.scenes) sc_ = std::make_unique<SceneRun>(w_, h_, batch_, metrics_.scene_bins, metrics_.scene_threshold);
+    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -834,6 +938,9 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     std::optional<std::vector<double>> s_ad[5]; // adm_scale0 .. adm_scale3, adm2
     if (ad_)
         for (auto &v : s_ad) v.emplace();
+    std::optional<std::vector<double>> s_sc; // --scenes: the scores, and the frames at which a scene starts
+    std::vector<size_t> scene_starts;
+    if (sc_) s_sc.emplace();
     std::optional<FrameScores> held;
     auto emit = [&](const FrameScores &r) {
         if (on_frame) on_frame(r);
@@ -842,6 +949,10 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (s_msssim && r.msssim) s_msssim->push_back(*r.msssim);
         if (s_ssimu && r.ssimulacra2) s_ssimu->push_back(*r.ssimulacra2);
         if (s_mo) { s_mo->push_back(*r.motion); s_mo2->push_back(*r.motion2); }
+        if (s_sc) {
+            s_sc->push_back(*r.scene_score);
+            if (compute_count == 0 || *r.scene_cut) scene_starts.push_back(compute_count);
+        }
         ++compute_count;
     };
     auto drain = [&](int i) {
@@ -866,6 +977,11 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
                 r.adm2 = v[4];
                 for (int k = 0; k < 5; ++k) s_ad[k]->push_back(v[k]);
             }
+            if (sc_) {
+                const std::pair<double, bool> v = sc_->pop();
+                r.scene_score = v.first;
+                r.scene_cut = v.second;
+            }
             if (mo_) {
                 r.motion = mo_->pop();
                 if (held) {
@@ -887,6 +1003,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (mo_) mo_->flush();
         if (vf_) vf_->flush();
         if (ad_) ad_->flush();
+        if (sc_) sc_->flush();
         in_flight[i] = true;
     };
 
@@ -957,6 +1074,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (mo_) mo_->push(fref);
         if (vf_) vf_->push(fref, fdis);
         if (ad_) ad_->push(fref, fdis);
+        if (sc_) sc_->push(fref);
         if (eng_[cur]) {
             set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
             set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
@@ -995,7 +1113,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_))
         throw NoFramesSelected();
     if (xp_) {
         std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
@@ -1015,6 +1133,10 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     if (ad_) {
         for (int k = 0; k < 4; ++k) res.adm_scale[k] = MetricAggregate::from(std::move(*s_ad[k]));
         res.adm2 = MetricAggregate::from(std::move(*s_ad[4]));
+    }
+    if (s_sc) {
+        res.scene_score = MetricAggregate::from(std::move(*s_sc));
+        res.scene_starts = std::move(scene_starts);
     }
     if (s_psnr) res.psnr = MetricAggregate::from(std::move(*s_psnr));
     if (s_ssim) res.ssim = MetricAggregate::from(std::move(*s_ssim));

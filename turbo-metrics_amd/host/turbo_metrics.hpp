@@ -37,6 +37,11 @@ struct Metrics {
     bool vif = false;
     // VMAF's ADM of every pair's lumas (include/turbo_metrics_adm.h, libturbometrics_adm.so): the CLI's -m adm; not an engine metric
     bool adm = false;
+    // scene cuts of the REFERENCE stream from luma histograms (include/turbo_metrics_scene.h, libturbometrics_scene.so): the CLI's
+    // --scenes, --scene-bins (8 .. 256, a power of two) and --scene-threshold (in (0, 1])
+    bool scenes = false;
+    uint32_t scene_bins = 64;
+    double scene_threshold = 0.5;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -72,6 +77,8 @@ struct MetricsResults {
     std::optional<MetricAggregate> motion, motion2; // their means are the sequence scores
     std::optional<MetricAggregate> vif_scale[4], vif; // likewise
     std::optional<MetricAggregate> adm2, adm_scale[4]; // likewise
+    std::optional<MetricAggregate> scene_score;        // --scenes: every frame's score against the frame before it (frame 0: 0)
+    std::vector<size_t> scene_starts;                  // the frame indices at which a scene begins: 0 and every cut
 };
 
 struct MetricsStats {
@@ -95,6 +102,8 @@ struct FrameScores {
     std::optional<double> motion, motion2;
     std::optional<double> vif_scale[4], vif;
     std::optional<double> adm2, adm_scale[4];
+    std::optional<double> scene_score;
+    std::optional<bool> scene_cut;
 };
 
 // ---- colour metadata (H.273 code points the reference understands, codec-bitstream/src/lib.rs:98-248) ----------
@@ -286,6 +295,7 @@ private:
     std::unique_ptr<struct XpsnrRun> xp_;                     // metrics_.xpsnr: the sequence's XPSNR state (library created at the first pair)
     std::unique_ptr<struct VifRun> vf_;                       // metrics_.vif: the VIF library's state (likewise; no history)
     std::unique_ptr<struct AdmRun> ad_;                       // metrics_.adm: the ADM library's state (likewise; no history)
+    std::unique_ptr<struct SceneRun> sc_;                     // metrics_.scenes: the reference stream's previous histogram (likewise)
     std::unique_ptr<struct MotionRun> mo_;                    // metrics_.motion: the reference stream's motion state (likewise)
     bool full_sums_ = false;                                  // settings replayed on an engine that is created later
     std::vector<std::pair<int, long long>> debug_params_;
