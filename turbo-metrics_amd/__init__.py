@@ -9,6 +9,7 @@ C ABI) with a host-side mirror of the reference's operator interface.
   vif     -- ctypes binding of include/turbo_metrics_vif.h (libturbometrics_vif.so): Vif, VMAF's VIF feature of frame pairs
   adm     -- ctypes binding of include/turbo_metrics_adm.h (libturbometrics_adm.so): Adm, VMAF's ADM feature of frame pairs
   scene   -- ctypes binding of include/turbo_metrics_scene.h (libturbometrics_scene.so): Scene, luma histograms and scene cuts
+  cambi   -- ctypes binding of include/turbo_metrics_cambi.h (libturbometrics_cambi.so): Cambi, VMAF's banding index of one stream
 
 There is no CPU implementation in this package: without the HIP library (or without a gfx950 GPU)
 the operators raise.
@@ -24,3 +25,5 @@ from . import adm  # noqa: F401,E402
 from .adm import Adm, AdmFrame  # noqa: F401,E402
 from . import scene  # noqa: F401,E402
 from .scene import Scene, SceneFrame  # noqa: F401,E402
+from . import cambi  # noqa: F401,E402
+from .cambi import Cambi, CambiFrame  # noqa: F401,E402

@@ -73,6 +73,11 @@ void usage(std::ostream &os)
           "                             and scene_starts, the frames at which a scene begins (YUV inputs; runs beside -m or alone)\n"
           "      --scene-threshold <X>  a frame whose scene_score reaches X starts a scene, 0 < X <= 1 (with --scenes) [default: 0.5]\n"
           "      --scene-bins <N>       histogram bins the score compares, after merging neighbours: 8, 16, 32, 64, 128 or 256 (with --scenes) [default: 64]\n"
+          "  -m cambi                   CAMBI, VMAF's banding index, of the DISTORTED stream: per-frame cambi and cambi_scale0 .. cambi_scale4, and their\n"
+          "                             sequence means (YUV inputs of at least 32 x 32; runs beside the other -m values or alone)\n"
+          "      --cambi-window <N>     side of the window the banding is looked for in, 3 ... 127 (with -m cambi) [default: 63 * width / 3840, at least 3]\n"
+          "      --cambi-topk <X>       share of the largest c-values a scale's score averages, 0 < X <= 1 (with -m cambi) [default: 0.6]\n"
+          "      --cambi-ref            also print cambi_ref and cambi_ref_scale0 .. cambi_ref_scale4 of the REFERENCE stream (with -m cambi)\n"
           "      --xpsnr-fps <N[/D]>    frame rate that picks XPSNR's temporal order (below 32: first order) [default: the Y4M F token, else 25]\n"
           "  -h, --help                 Print help\n"
           "  -V, --version              Print version\n";
@@ -138,7 +143,7 @@ int main(int argc, char **argv)
     SourceHints hints;
     uint32_t batch = 0 /* 0: chosen from the picture size */, device = 0, devices = 1, ranks = 0 /* 0: not asked for */, in_flight_pairs = 2;
     uint32_t xpsnr_fps_num = 0, xpsnr_fps_den = 1; // --xpsnr-fps (0: not given)
-    bool pipeline = true, full_sums = false, in_flight_given = false, scene_values_given = false;
+    bool pipeline = true, full_sums = false, in_flight_given = false, scene_values_given = false, cambi_values_given = false;
     enum class Loop { Batched, Reference, Deferred } loop = Loop::Batched;
     std::vector<std::pair<int, long long>> tune;
 
@@ -173,6 +178,7 @@ int main(int argc, char **argv)
             else if (s == "xpsnr") metrics.xpsnr = true;
             else if (s == "vif") metrics.vif = true;
             else if (s == "adm") metrics.adm = true;
+            else if (s == "cambi") metrics.cambi = true;
             else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2]");
         } else if (a.rfind("-m", 0) == 0 && a.size() > 2 && a[1] == 'm') { // -mpsnr
             const std::string s = a.substr(2);
@@ -181,6 +187,7 @@ int main(int argc, char **argv)
             else if (s == "xpsnr") metrics.xpsnr = true;
             else if (s == "vif") metrics.vif = true;
             else if (s == "adm") metrics.adm = true;
+            else if (s == "cambi") metrics.cambi = true;
             else return bad("invalid value '" + s + "' for '--metrics <METRICS>'");
         } else if (a == "--every") { if (!u32(opts.every)) return bad("invalid value for '--every <EVERY>'"); }
         else if (a == "--skip") { if (!u32(opts.skip)) return bad("invalid value for '--skip <SKIP>'"); }
@@ -223,6 +230,24 @@ int main(int argc, char **argv)
             metrics.scene_bins = n;
             scene_values_given = true;
         }
+        else if (a == "--cambi-window") {
+            std::string v;
+            if (!value(v)) return bad("a value is required for '--cambi-window <N>' but none was supplied");
+            uint32_t n = 0;
+            if (!parse_u32(v, n) || n < 3 || n > 127) return bad("invalid value '" + v + "' for '--cambi-window <N>'\n  [3 ... 127]");
+            metrics.cambi_window = n;
+            cambi_values_given = true;
+        }
+        else if (a == "--cambi-topk") {
+            std::string v;
+            if (!value(v)) return bad("a value is required for '--cambi-topk <X>' but none was supplied");
+            char *end = nullptr;
+            const double x = strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(x > 0.0 && x <= 1.0)) return bad("invalid value '" + v + "' for '--cambi-topk <X>'\n  [0 < X <= 1]");
+            metrics.cambi_topk = x;
+            cambi_values_given = true;
+        }
+        else if (a == "--cambi-ref") { metrics.cambi_ref = true; cambi_values_given = true; }
         else if (a == "--xpsnr-fps") {
             std::string v;
             if (!value(v)) return bad("a value is required for '--xpsnr-fps <N[/D]>'");
@@ -248,6 +273,11 @@ int main(int argc, char **argv)
     }
     if (pos.size() != 2) return bad("the following required arguments were not provided:\n  <REFERENCE>\n  <DISTORTED>");
     if (scene_values_given && !metrics.scenes) return bad("'--scene-threshold <X>' and '--scene-bins <N>' belong to '--scenes'");
+    if (cambi_values_given && !metrics.cambi) return bad("'--cambi-window <N>', '--cambi-topk <X>' and '--cambi-ref' belong to '-m cambi'");
+    if (metrics.cambi) { // CAMBI, like VIF and ADM, runs on one device in the batched loop
+        const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
+        if (why) { log_line(L_ERROR, kTarget, std::string("-m cambi does not run with ") + why); return EXIT_FAILURE; }
+    }
     if (metrics.scenes) { // a frame is compared with the frame before it in ONE stream on one device
         const char *why = devices != 1 ? "--devices (shards would cut the sequence)"
                         : ranks > 0 ? "--ranks (shards would cut the sequence)"
@@ -526,7 +556,7 @@ int main(int argc, char **argv)
 
     std::unique_ptr<TurboMetrics> turbo;
     try {
-        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
+        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
         // a source that knows its length never needs more slots than it has pairs (a single image pair: one slot, one engine)
         const size_t known = std::min(source_ref->frame_count(), source_dis->frame_count());
         if (batch == 0) batch = auto_batch(source_ref->width(), source_ref->height());

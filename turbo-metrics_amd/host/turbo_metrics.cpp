@@ -4,6 +4,7 @@
 #include "../../include/turbo_metrics_xpsnr.h"
 #include "../../include/turbo_metrics_motion.h"
 #include "../../include/turbo_metrics_scene.h"
+#include "../../include/turbo_metrics_cambi.h"
 #include "../../include/turbo_metrics_vif.h"
 #include "../../include/turbo_metrics_adm.h"
 #include <dlfcn.h>
@@ -460,6 +461,96 @@ struct SceneRun {
     }
 };
 
+// ---- CAMBI ---------------------------------------------------------------------------------------------------------
+// libturbometrics_cambi.so, loaded at run time like the scene library (a CLI run without -m cambi never loads it).  The luma of ONE
+// stream of every kept pair is handed over as a TM_MEM_HOST copy and computed batch by batch in stream order; a picture's six scores
+// (five scales, cambi) wait in `ready` until the engine's scores of the same pair are drained.  The scores are the library's host
+// function: nothing here restates the definition.  No history: --every is fine.
+struct CambiRun {
+    void *lib = nullptr;
+    int (*create)(tm_cambi **, uint32_t, uint32_t, int, uint32_t, uint32_t, double, double, uint32_t) = nullptr;
+    void (*destroy)(tm_cambi *) = nullptr;
+    int (*set_frame)(tm_cambi *, uint32_t, const void *, size_t, int) = nullptr;
+    int (*compute_async)(tm_cambi *, uint32_t) = nullptr;
+    int (*sync)(tm_cambi *) = nullptr;
+    int (*get)(tm_cambi *, uint32_t, uint32_t, tm_cambi_frame *) = nullptr;
+    int (*scores)(const tm_cambi_frame *, uint32_t, double *) = nullptr;
+    uint32_t (*window_of)(uint32_t, uint32_t) = nullptr;
+    tm_cambi *s = nullptr;
+    uint32_t w, h, batch, window;
+    double topk;
+    int layout = -1;
+    uint32_t bits = 8, filled = 0;
+    std::vector<tm_cambi_frame> out;
+    std::deque<std::array<double, 6>> ready;
+
+    CambiRun(uint32_t w_, uint32_t h_, uint32_t batch_, uint32_t window_, double topk_) : w(w_), h(h_), batch(batch_), window(window_), topk(topk_)
+    {
+        const char *path = getenv("TM_CAMBI_LIB");
+        lib = dlopen(path ? path : "libturbometrics_cambi.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("-m cambi needs libturbometrics_cambi.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_cambi_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_cambi_destroy");
+        set_frame = (decltype(set_frame))dlsym(lib, "tm_cambi_set_frame");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_cambi_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_cambi_sync");
+        get = (decltype(get))dlsym(lib, "tm_cambi_get");
+        scores = (decltype(scores))dlsym(lib, "tm_cambi_scores");
+        window_of = (decltype(window_of))dlsym(lib, "tm_cambi_window");
+        if (!create || !destroy || !set_frame || !compute_async || !sync || !get || !scores || !window_of)
+            throw std::runtime_error("libturbometrics_cambi.so does not export include/turbo_metrics_cambi.h");
+    }
+    ~CambiRun()
+    {
+        if (s) destroy(s);
+        if (lib) dlclose(lib);
+    }
+    void push(const HwFrame &r)
+    {
+        int l;
+        uint32_t b;
+        switch (r.kind) {
+        case HwFrame::NvDecNV12: l = TM_CAMBI_Y8; b = 8; break;
+        case HwFrame::NvDecP016: l = TM_CAMBI_Y16_MSB; b = 10; break;
+        case HwFrame::Planar420: b = (uint32_t)r.bits; l = b == 8 ? TM_CAMBI_Y8 : TM_CAMBI_Y16_LOW; break;
+        case HwFrame::Planar420P10: l = TM_CAMBI_Y10_PACKED; b = 10; break;
+        default: throw std::runtime_error("cambi needs YUV input (Y4M, raw planar YUV or decoded video), not RGB images");
+        }
+        if (!s) {
+            layout = l; bits = b;
+            const int rc = create(&s, w, h, layout, bits, window, topk, TM_CAMBI_DEFAULT_TVI_THRESHOLD, batch);
+            if (rc == TM_ERR_UNSUPPORTED) throw std::runtime_error("cambi takes pictures of at least 32 x 32 and at most 2^31 samples, at 8 to 16 bits in a layout that carries them, a window of 0 or 3 .. 127 and a topk in (0, 1]");
+            chk(rc, "tm_cambi_create");
+        } else if (l != layout || b != bits) {
+            throw std::runtime_error("cambi: the YUV layout changed inside the stream");
+        }
+        chk(set_frame(s, filled, r.data, r.pitch, r.device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_cambi_set_frame");
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(s, filled), "tm_cambi_compute_async");
+        chk(sync(s), "tm_cambi_sync");
+        out.resize(filled);
+        chk(get(s, 0, filled, out.data()), "tm_cambi_get");
+        const uint32_t win = window_of(w, window);
+        for (const tm_cambi_frame &f : out) {
+            std::array<double, 6> v;
+            chk(scores(&f, win, v.data()), "tm_cambi_scores");
+            ready.push_back(v);
+        }
+        filled = 0;
+    }
+    std::array<double, 6> pop()
+    {
+        if (ready.empty()) throw std::logic_error("cambi: a picture's result is missing");
+        const std::array<double, 6> v = ready.front();
+        ready.pop_front();
+        return v;
+    }
+};
+
 // ---- VIF -----------------------------------------------------------------------------------------------------------
 // libturbometrics_vif.so, loaded at run time like the XPSNR and motion libraries (a CLI run without -m vif never loads it).  The lumas
 // of every kept pair are handed over as TM_MEM_HOST copies and computed batch by batch in stream order; a pair's five scores wait in
@@ -653,7 +744,9 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
     if (metrics_.vif) vf_ = std::make_unique<VifRun>(w_, h_, batch_);
     if (metrics_.adm) ad_ = std::make_unique<AdmRun>(w_, h_, batch_);
     if (metrics_.scenes) sc_ = std::make_unique<SceneRun>(w_, h_, batch_, metrics_.scene_bins, metrics_.scene_threshold);
-    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
+    if (metrics_.cambi) cb_ = std::make_unique<CambiRun>(w_, h_, batch_, metrics_.cambi_window, metrics_.cambi_topk);
+    if (metrics_.cambi && metrics_.cambi_ref) cbr_ = std::make_unique<CambiRun>(w_, h_, batch_, metrics_.cambi_window, metrics_.cambi_topk);
+    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -941,6 +1034,11 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     std::optional<std::vector<double>> s_sc; // --scenes: the scores, and the frames at which a scene starts
     std::vector<size_t> scene_starts;
     if (sc_) s_sc.emplace();
+    std::optional<std::vector<double>> s_cb[6], s_cbr[6]; // cambi_scale0 .. cambi_scale4, cambi; the reference stream's
+    if (cb_)
+        for (auto &v : s_cb) v.emplace();
+    if (cbr_)
+        for (auto &v : s_cbr) v.emplace();
     std::optional<FrameScores> held;
     auto emit = [&](const FrameScores &r) {
         if (on_frame) on_frame(r);
@@ -982,6 +1080,18 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
                 r.scene_score = v.first;
                 r.scene_cut = v.second;
             }
+            if (cb_) {
+                const std::array<double, 6> v = cb_->pop();
+                for (int k = 0; k < 5; ++k) r.cambi_scale[k] = v[k];
+                r.cambi = v[5];
+                for (int k = 0; k < 6; ++k) s_cb[k]->push_back(v[k]);
+            }
+            if (cbr_) {
+                const std::array<double, 6> v = cbr_->pop();
+                for (int k = 0; k < 5; ++k) r.cambi_ref_scale[k] = v[k];
+                r.cambi_ref = v[5];
+                for (int k = 0; k < 6; ++k) s_cbr[k]->push_back(v[k]);
+            }
             if (mo_) {
                 r.motion = mo_->pop();
                 if (held) {
@@ -1004,6 +1114,8 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (vf_) vf_->flush();
         if (ad_) ad_->flush();
         if (sc_) sc_->flush();
+        if (cb_) cb_->flush();
+        if (cbr_) cbr_->flush();
         in_flight[i] = true;
     };
 
@@ -1075,6 +1187,8 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (vf_) vf_->push(fref, fdis);
         if (ad_) ad_->push(fref, fdis);
         if (sc_) sc_->push(fref);
+        if (cb_) cb_->push(fdis);
+        if (cbr_) cbr_->push(fref);
         if (eng_[cur]) {
             set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
             set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
@@ -1113,7 +1227,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_))
         throw NoFramesSelected();
     if (xp_) {
         std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
@@ -1137,6 +1251,14 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     if (s_sc) {
         res.scene_score = MetricAggregate::from(std::move(*s_sc));
         res.scene_starts = std::move(scene_starts);
+    }
+    if (cb_) {
+        for (int k = 0; k < 5; ++k) res.cambi_scale[k] = MetricAggregate::from(std::move(*s_cb[k]));
+        res.cambi = MetricAggregate::from(std::move(*s_cb[5]));
+    }
+    if (cbr_) {
+        for (int k = 0; k < 5; ++k) res.cambi_ref_scale[k] = MetricAggregate::from(std::move(*s_cbr[k]));
+        res.cambi_ref = MetricAggregate::from(std::move(*s_cbr[5]));
     }
     if (s_psnr) res.psnr = MetricAggregate::from(std::move(*s_psnr));
     if (s_ssim) res.ssim = MetricAggregate::from(std::move(*s_ssim));

@@ -42,6 +42,11 @@ struct Metrics {
     bool scenes = false;
     uint32_t scene_bins = 64;
     double scene_threshold = 0.5;
+    // CAMBI, VMAF's banding index, of the DISTORTED stream (include/turbo_metrics_cambi.h, libturbometrics_cambi.so): the CLI's -m cambi,
+    // --cambi-window (0: derived from the width), --cambi-topk, and --cambi-ref (the reference stream's as well); not an engine metric
+    bool cambi = false, cambi_ref = false;
+    uint32_t cambi_window = 0;
+    double cambi_topk = 0.6;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -79,6 +84,8 @@ struct MetricsResults {
     std::optional<MetricAggregate> adm2, adm_scale[4]; // likewise
     std::optional<MetricAggregate> scene_score;        // --scenes: every frame's score against the frame before it (frame 0: 0)
     std::vector<size_t> scene_starts;                  // the frame indices at which a scene begins: 0 and every cut
+    std::optional<MetricAggregate> cambi, cambi_scale[5];         // -m cambi: the distorted stream; their means are the sequence scores
+    std::optional<MetricAggregate> cambi_ref, cambi_ref_scale[5]; // --cambi-ref: the reference stream
 };
 
 struct MetricsStats {
@@ -104,6 +111,7 @@ struct FrameScores {
     std::optional<double> adm2, adm_scale[4];
     std::optional<double> scene_score;
     std::optional<bool> scene_cut;
+    std::optional<double> cambi, cambi_scale[5], cambi_ref, cambi_ref_scale[5];
 };
 
 // ---- colour metadata (H.273 code points the reference understands, codec-bitstream/src/lib.rs:98-248) ----------
@@ -295,6 +303,7 @@ private:
     std::unique_ptr<struct XpsnrRun> xp_;                     // metrics_.xpsnr: the sequence's XPSNR state (library created at the first pair)
     std::unique_ptr<struct VifRun> vf_;                       // metrics_.vif: the VIF library's state (likewise; no history)
     std::unique_ptr<struct AdmRun> ad_;                       // metrics_.adm: the ADM library's state (likewise; no history)
+    std::unique_ptr<struct CambiRun> cb_, cbr_;               // metrics_.cambi / cambi_ref: the CAMBI library's state per stream (likewise; no history)
     std::unique_ptr<struct SceneRun> sc_;                     // metrics_.scenes: the reference stream's previous histogram (likewise)
     std::unique_ptr<struct MotionRun> mo_;                    // metrics_.motion: the reference stream's motion state (likewise)
     bool full_sums_ = false;                                  // settings replayed on an engine that is created later
