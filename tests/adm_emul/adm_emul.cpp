@@ -126,6 +126,8 @@ void run(Launch L)
 
 extern "C" {
 unsigned ae_desc_size() { return (unsigned)sizeof(TmAdmDesc); }
+// the tile of k_adm (band pixels of a scale): tests/geom_sweep.py builds its sizes from it
+void ae_tile(int *out) { out[0] = TMA_TX; out[1] = TMA_TY; }
 
 int ae_mirror(int p, int n) { return tma::mirror(p, n); }
 

@@ -79,6 +79,8 @@ unsigned blocks(unsigned long long n) { return (unsigned)((n + TMC_THREADS - 1) 
 extern "C" {
 unsigned ce_desc_size() { return (unsigned)sizeof(TmCambiDesc); }
 unsigned ce_res_size() { return (unsigned)sizeof(TmCambiRes); }
+// the mask kernel's tile and the columns of one workgroup of the c-value kernel: tests/geom_sweep.py builds its sizes from them
+void ce_tile(unsigned *out) { out[0] = TMC_MASK_TW; out[1] = TMC_MASK_TH; out[2] = TMC_MAX_COLS; }
 
 // geometry of the library for these arguments: out = w[5], h[5], off[5], tot, window, oc, band_rows as 64-bit words; 0, or -1 (refused)
 int ce_geom(unsigned w, unsigned h, int layout, unsigned bits, unsigned window, double topk, double thr, unsigned long long *out)

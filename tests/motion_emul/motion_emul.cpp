@@ -87,6 +87,8 @@ void run(const Launch &L)
 
 extern "C" {
 unsigned me_desc_size() { return (unsigned)sizeof(TmMotionDesc); }
+// the tile of k_motion: tests/geom_sweep.py builds its sizes from it
+void me_tile(int *out) { out[0] = TMM_TW; out[1] = TMM_TH; }
 
 // a whole sequence: pictures [0, sum(batches)) as descriptors; a negative batch entry -n is a reset followed by a batch of n.
 // out[f] = sad; blurred (optional): the history plane after the last batch, w x h uint16.  0, or -1 (unsupported geometry)

@@ -81,6 +81,9 @@ void run(const Launch &L)
 
 extern "C" {
 unsigned se_desc_size() { return (unsigned)sizeof(TmSceneDesc); }
+// samples per band (about), rows in flight per lane, most rows of a band, samples one pass of the lanes covers: tests/geom_sweep.py
+// builds its sizes from them
+void se_tile(unsigned *out) { out[0] = TMS_BAND_SAMPLES; out[1] = TMS_ROWS; out[2] = TMS_BAND_ROWS_MAX; out[3] = 4 * TMS_THREADS; }
 unsigned se_bands(unsigned w, unsigned h, int layout, unsigned bits)
 {
     TmSceneGeom g;

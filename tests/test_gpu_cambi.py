@@ -203,6 +203,36 @@ def test_cli_cambi_parameters_ref_and_other_metrics(tmp_path):
                 assert [json.loads(q)["cambi"] for q in with_c[:5]] == [r[0] for r in _binding(dis, 8)]
 
 
+def test_cli_every_feature_library_at_once_equals_each_alone(tmp_path):
+    """7 pictures of 160 x 96 in batches of 3 (a partial last batch) with all six feature libraries and the engine in flight for every
+    batch: each column is the column of a run that selects that metric alone; and with --every 2 for the metrics that keep no history"""
+    from tests import vif_util
+    w, h, n = 160, 96, 7
+    pairs = [vif_util.pair(w, h, 8, "blurred", seed=i) for i in range(n)]
+    a, b = str(tmp_path / "a.y4m"), str(tmp_path / "b.y4m")
+    _y4m(a, w, h, [p[0] for p in pairs], 8, 1)
+    # pictures 1, 2, 5 and 6 band (CAMBI above 0); --every 2 keeps 0, 2, 4, 6: both kinds are in either run
+    _y4m(b, w, h, [U.picture(w, h, 8, "mixed", seed=i) if i % 4 in (1, 2) else p[1] for i, p in enumerate(pairs)], 8, 2)
+
+    def run(sel, *extra):
+        return [json.loads(x) for x in _cli(a, b, *sel, "--batch", "3", *extra, "--output", "json-lines").splitlines() if x.strip()]
+    alone = {"psnr": ["-m", "psnr"], "xpsnr": ["-m", "xpsnr"], "vif": ["-m", "vif"], "adm": ["-m", "adm"], "cambi": ["-m", "cambi"],
+             "motion": ["--motion"], "scenes": ["--scenes"]}
+    for extra, names in (((), list(alone)), (("--every", "2"), ["psnr", "vif", "adm", "cambi"])):
+        together = run([x for k in names for x in alone[k]], *extra)
+        assert len(together) == (n if not extra else (n + 1) // 2) + 1
+        seen = set()
+        for k in names:
+            one = run(alone[k], *extra)
+            assert len(one) == len(together)
+            for p, q in zip(one, together):
+                assert p and all(q[c] == v for c, v in p.items()), (k, extra, p, q)  # the per-picture lines and the summary line
+                seen |= set(p)
+        assert all(set(q) <= seen for q in together)  # and nothing besides
+        frames = [q for q in together if "frame_count" not in q]
+        assert any(q["cambi"] > 0 for q in frames) and any(q["cambi"] == 0 for q in frames)  # the banded pictures band, the others do not
+
+
 def test_cli_cambi_refuses_rgb_images(tmp_path):
     a = str(tmp_path / "a.ppm")
     with open(a, "wb") as f:

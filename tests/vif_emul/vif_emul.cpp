@@ -118,6 +118,8 @@ void run(Launch L)
 
 extern "C" {
 unsigned ve_desc_size() { return (unsigned)sizeof(TmVifDesc); }
+// the tile of k_vif (pixels of a scale): tests/geom_sweep.py builds its sizes from it
+void ve_tile(int *out) { out[0] = TMV_TW; out[1] = TMV_TH; }
 
 // taps of filter s into out[17]; returns their number
 int ve_filter(int s, unsigned *out)

@@ -79,6 +79,13 @@ void run_blocks(const Launch &L)
 
 extern "C" {
 unsigned xe_desc_size() { return (unsigned)sizeof(TmXpsnrDesc); }
+// rows per LDS band, and the block size of a picture (0: refused): tests/geom_sweep.py builds its sizes from them
+int xe_band() { return TMX_BAND; }
+int xe_block(unsigned w, unsigned h, int layout, unsigned bits)
+{
+    TmXpsnrGeom g;
+    return tmx_make_geom(&g, w, h, layout, bits, 25, 1) ? 0 : (g.small ? -1 : g.b);
+}
 
 // a whole sequence: frames [0, sum(batches)) as descriptors desc[2 f + side]; out[3 f + c] = wsse64.  0, or -1 (unsupported geometry)
 int xe_sequence(unsigned w, unsigned h, int layout, unsigned bits, unsigned fps_num, unsigned fps_den, int nbatches, const int *batches,

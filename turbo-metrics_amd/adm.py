@@ -92,7 +92,8 @@ class Adm:
     """ADM of `batch` reference / distorted pairs per compute.  layout: "y8" | "y16_msb" | "y16_low" | "y10_packed"
     (include/turbo_metrics_adm.h).  A picture is its luma plane: a numpy array (copied) or a torch tensor (device tensors are read in
     place, pinned host tensors by DMA: both must stay alive until compute returns).  The two planes of a pair live in the same kind
-    of memory."""
+    of memory.
+    compute(n) is compute_async(n) then sync(): the two halves let several objects, each on its own stream, be in flight at once."""
 
     def __init__(self, w, h, layout="y8", bits=8, batch=1):
         self._L = lib()
@@ -166,6 +167,14 @@ class Adm:
     def compute(self, n):
         """slots [0, n); waits for the result"""
         _chk(self._L.tm_adm_compute_async(self._h, int(n)), "tm_adm_compute_async")
+        _chk(self._L.tm_adm_sync(self._h), "tm_adm_sync")
+
+    def compute_async(self, n):
+        """tm_adm_compute_async: queues slots [0, n) on this object's stream and returns; the planes stay alive until sync()"""
+        _chk(self._L.tm_adm_compute_async(self._h, int(n)), "tm_adm_compute_async")
+
+    def sync(self):
+        """tm_adm_sync: waits for what compute_async queued"""
         _chk(self._L.tm_adm_sync(self._h), "tm_adm_sync")
 
     def frames(self, n, first=0):

@@ -111,7 +111,8 @@ class Cambi:
     """CAMBI of `batch` pictures per compute.  layout: "y8" | "y16_msb" | "y16_low" | "y10_packed" (include/turbo_metrics_cambi.h);
     window: 0 derives it from the width.  A picture is its luma plane: a numpy array (copied) or a torch tensor (device tensors are
     read in place, pinned host tensors by DMA: both must stay alive until compute returns).  Stateless: nothing is kept between
-    computes."""
+    computes.
+    compute(n) is compute_async(n) then sync(): the two halves let several objects, each on its own stream, be in flight at once."""
 
     def __init__(self, w, h, layout="y8", bits=8, window=0, topk=DEFAULT_TOPK, tvi_threshold=DEFAULT_TVI_THRESHOLD, batch=1):
         self._L = lib()
@@ -186,6 +187,14 @@ class Cambi:
     def compute(self, n):
         """CAMBI of slots [0, n); waits for the result"""
         _chk(self._L.tm_cambi_compute_async(self._h, int(n)), "tm_cambi_compute_async")
+        _chk(self._L.tm_cambi_sync(self._h), "tm_cambi_sync")
+
+    def compute_async(self, n):
+        """tm_cambi_compute_async: queues slots [0, n) on this object's stream and returns; the planes stay alive until sync()"""
+        _chk(self._L.tm_cambi_compute_async(self._h, int(n)), "tm_cambi_compute_async")
+
+    def sync(self):
+        """tm_cambi_sync: waits for what compute_async queued"""
         _chk(self._L.tm_cambi_sync(self._h), "tm_cambi_sync")
 
     def frames(self, n, first=0):

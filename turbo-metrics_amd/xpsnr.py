@@ -75,7 +75,8 @@ class XpsnrFrame(NamedTuple):
 class Xpsnr:
     """XPSNR of one sequence, `batch` pictures per compute.  layout: "nv12" | "p016" | "i420" | "i420p10" (include/turbo_metrics_xpsnr.h).
     A picture is the tuple of its planes: (Y, CbCr) for nv12 / p016, (Y, Cb, Cr) otherwise; numpy arrays (copied) or torch tensors
-    (device tensors are read in place, pinned host tensors by DMA: both must stay alive until compute returns)."""
+    (device tensors are read in place, pinned host tensors by DMA: both must stay alive until compute returns).
+    compute(n) is compute_async(n) then sync(): the two halves let several objects, each on its own stream, be in flight at once."""
 
     def __init__(self, w, h, layout="nv12", bits=8, fps=(25, 1), batch=1):
         self._L = lib()
@@ -163,6 +164,14 @@ class Xpsnr:
     def compute(self, n):
         """slots [0, n) continue the sequence; waits for the result"""
         _chk(self._L.tm_xpsnr_compute_async(self._h, int(n)), "tm_xpsnr_compute_async")
+        _chk(self._L.tm_xpsnr_sync(self._h), "tm_xpsnr_sync")
+
+    def compute_async(self, n):
+        """tm_xpsnr_compute_async: queues slots [0, n) on this object's stream and returns; the planes stay alive until sync()"""
+        _chk(self._L.tm_xpsnr_compute_async(self._h, int(n)), "tm_xpsnr_compute_async")
+
+    def sync(self):
+        """tm_xpsnr_sync: waits for what compute_async queued"""
         _chk(self._L.tm_xpsnr_sync(self._h), "tm_xpsnr_sync")
 
     def frames(self, n, first=0):
