@@ -10,6 +10,7 @@ C ABI) with a host-side mirror of the reference's operator interface.
   adm     -- ctypes binding of include/turbo_metrics_adm.h (libturbometrics_adm.so): Adm, VMAF's ADM feature of frame pairs
   scene   -- ctypes binding of include/turbo_metrics_scene.h (libturbometrics_scene.so): Scene, luma histograms and scene cuts
   cambi   -- ctypes binding of include/turbo_metrics_cambi.h (libturbometrics_cambi.so): Cambi, VMAF's banding index of one stream
+  flip    -- ctypes binding of include/turbo_metrics_flip.h (libturbometrics_flip.so): Flip, the LDR-FLIP difference map of picture pairs
 
 There is no CPU implementation in this package: without the HIP library (or without a gfx950 GPU)
 the operators raise.
@@ -27,3 +28,5 @@ from . import scene  # noqa: F401,E402
 from .scene import Scene, SceneFrame  # noqa: F401,E402
 from . import cambi  # noqa: F401,E402
 from .cambi import Cambi, CambiFrame  # noqa: F401,E402
+from . import flip  # noqa: F401,E402
+from .flip import Flip, FlipFrame  # noqa: F401,E402

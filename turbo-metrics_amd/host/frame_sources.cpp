@@ -43,7 +43,7 @@ ImageFormat probe_image(const unsigned char *s, size_t len)
     static const unsigned char png[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
     if (!memcmp(s, png, 8)) return ImageFormat::PNG;
     if (s[0] == 'P' && s[1] == '6' && (s[2] == '\n' || s[2] == ' ' || s[2] == '\r' || s[2] == '\t')) return ImageFormat::PPM;
-    if (s[0] == 'P' && s[1] == 'F' && (s[2] == '\n' || s[2] == ' ' || s[2] == '\r')) return ImageFormat::PFM;
+    if (s[0] == 'P' && (s[1] == 'F' || s[1] == 'f') && (s[2] == '\n' || s[2] == ' ' || s[2] == '\r')) return ImageFormat::PFM;
     if (s[0] == 0xFF && s[1] == 0xD8 && s[2] == 0xFF) return ImageFormat::JPEG;
     if (!memcmp(s, "GIF8", 4) || !memcmp(s, "BM", 2) || (!memcmp(s, "RIFF", 4) && !memcmp(s + 8, "WEBP", 4)) ||
         !memcmp(s, "II*\0", 4) || !memcmp(s, "MM\0*", 4) || !memcmp(s, "qoif", 4))
@@ -257,7 +257,7 @@ CpuImg decode_pnm(const unsigned char *d, size_t len)
         if (t.empty()) fail("PNM: truncated header");
         return t;
     };
-    const bool pfm = d[1] == 'F';
+    const bool gray = d[1] == 'f', pfm = d[1] == 'F' || gray; // "Pf": one channel, handed out as R = G = B
     CpuImg img;
     const unsigned long pw = std::stoul(token()), ph = std::stoul(token());
     check_dims("PNM", pw, ph);
@@ -269,11 +269,18 @@ CpuImg decode_pnm(const unsigned char *d, size_t len)
     const size_t n = (size_t)img.width * img.height * 3;
     if (pfm) {
         const double scale = std::stod(third);
-        if (pos + n * 4 > len) fail("PFM: truncated");
+        if (pos + n * 4 / (gray ? 3 : 1) > len) fail("PFM: truncated");
         img.sample_type = CpuImg::F32;
         img.data.resize(n * 4);
         const size_t row = (size_t)img.width * 12;
-        for (uint32_t y = 0; y < img.height; ++y) { // PFM rows run bottom to top
+        for (uint32_t y = 0; gray && y < img.height; ++y) {
+            const unsigned char *src = d + pos + (size_t)(img.height - 1 - y) * img.width * 4;
+            unsigned char *dst = img.data.data() + (size_t)y * row;
+            for (size_t x = 0; x < img.width; ++x)
+                for (int c = 0; c < 3; ++c)
+                    for (int b = 0; b < 4; ++b) dst[x * 12 + c * 4 + b] = src[x * 4 + (scale < 0 ? b : 3 - b)];
+        }
+        for (uint32_t y = 0; !gray && y < img.height; ++y) { // PFM rows run bottom to top
             const unsigned char *src = d + pos + (size_t)(img.height - 1 - y) * row;
             unsigned char *dst = img.data.data() + (size_t)y * row;
             if (scale < 0) memcpy(dst, src, row);
@@ -290,6 +297,16 @@ CpuImg decode_pnm(const unsigned char *d, size_t len)
             for (size_t i = 0; i + 1 < img.data.size(); i += 2) std::swap(img.data[i], img.data[i + 1]);
     }
     return img;
+}
+
+void write_pfm_gray(const std::string &path, uint32_t w, uint32_t h, const float *data)
+{
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) fail("cannot write '" + path + "': " + strerror(errno));
+    bool ok = fprintf(f, "Pf\n%u %u\n-1.0\n", w, h) > 0;
+    for (uint32_t y = h; ok && y-- > 0;) ok = fwrite(data + (size_t)y * w, sizeof(float), w, f) == w;
+    ok = fclose(f) == 0 && ok;
+    if (!ok) fail("cannot write '" + path + "'");
 }
 
 // ---- ImageFrameSource ------------------------------------------------------------------------------------------------

@@ -42,6 +42,8 @@ struct CpuImg { // img.rs:40-48
 };
 
 // decoders (throw std::runtime_error with the reason)
+// a one-channel PFM ("Pf", little-endian, rows bottom to top) of w x h floats given top to bottom; decode_pnm reads it back as grey RGB
+void write_pfm_gray(const std::string &path, uint32_t w, uint32_t h, const float *data);
 CpuImg decode_png(const unsigned char *data, size_t len);                      // the first frame
 std::vector<CpuImg> decode_png_frames(const unsigned char *data, size_t len); // every frame (animated PNG: composed onto the canvas)
 CpuImg decode_pnm(const unsigned char *data, size_t len);

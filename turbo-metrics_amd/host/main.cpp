@@ -75,6 +75,10 @@ void usage(std::ostream &os)
           "      --scene-bins <N>       histogram bins the score compares, after merging neighbours: 8, 16, 32, 64, 128 or 256 (with --scenes) [default: 64]\n"
           "  -m cambi                   CAMBI, VMAF's banding index, of the DISTORTED stream: per-frame cambi and cambi_scale0 .. cambi_scale4, and their\n"
           "                             sequence means (YUV inputs of at least 32 x 32; runs beside the other -m values or alone)\n"
+          "  -m flip                    LDR-FLIP, the perceptual difference map of pairs of 8-bit RGB images (PNG, PPM): per-pair flip (the map's mean),\n"
+          "                             flip_min and flip_max, after all other columns; alone or beside the other -m values\n"
+          "      --flip-ppd <X>         pixels per degree of the viewing condition, 8 ... 256; above 74.04 the run ends with an error (with -m flip) [default: 67.02]\n"
+          "      --flip-map <PREFIX>    write every pair's FLIP map as a one-channel PFM, PREFIX000000.pfm, PREFIX000001.pfm, ... (with -m flip)\n"
           "      --cambi-window <N>     side of the window the banding is looked for in, 3 ... 127 (with -m cambi) [default: 63 * width / 3840, at least 3]\n"
           "      --cambi-topk <X>       share of the largest c-values a scale's score averages, 0 < X <= 1 (with -m cambi) [default: 0.6]\n"
           "      --cambi-ref            also print cambi_ref and cambi_ref_scale0 .. cambi_ref_scale4 of the REFERENCE stream (with -m cambi)\n"
@@ -143,7 +147,7 @@ int main(int argc, char **argv)
     SourceHints hints;
     uint32_t batch = 0 /* 0: chosen from the picture size */, device = 0, devices = 1, ranks = 0 /* 0: not asked for */, in_flight_pairs = 2;
     uint32_t xpsnr_fps_num = 0, xpsnr_fps_den = 1; // --xpsnr-fps (0: not given)
-    bool pipeline = true, full_sums = false, in_flight_given = false, scene_values_given = false, cambi_values_given = false;
+    bool pipeline = true, full_sums = false, in_flight_given = false, scene_values_given = false, cambi_values_given = false, flip_values_given = false;
     enum class Loop { Batched, Reference, Deferred } loop = Loop::Batched;
     std::vector<std::pair<int, long long>> tune;
 
@@ -179,6 +183,7 @@ int main(int argc, char **argv)
             else if (s == "vif") metrics.vif = true;
             else if (s == "adm") metrics.adm = true;
             else if (s == "cambi") metrics.cambi = true;
+            else if (s == "flip") metrics.flip = true;
             else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2]");
         } else if (a.rfind("-m", 0) == 0 && a.size() > 2 && a[1] == 'm') { // -mpsnr
             const std::string s = a.substr(2);
@@ -188,6 +193,7 @@ int main(int argc, char **argv)
             else if (s == "vif") metrics.vif = true;
             else if (s == "adm") metrics.adm = true;
             else if (s == "cambi") metrics.cambi = true;
+            else if (s == "flip") metrics.flip = true;
             else return bad("invalid value '" + s + "' for '--metrics <METRICS>'");
         } else if (a == "--every") { if (!u32(opts.every)) return bad("invalid value for '--every <EVERY>'"); }
         else if (a == "--skip") { if (!u32(opts.skip)) return bad("invalid value for '--skip <SKIP>'"); }
@@ -247,6 +253,19 @@ int main(int argc, char **argv)
             metrics.cambi_topk = x;
             cambi_values_given = true;
         }
+        else if (a == "--flip-ppd") {
+            std::string v;
+            if (!value(v)) return bad("a value is required for '--flip-ppd <X>' but none was supplied");
+            char *end = nullptr;
+            const double x = strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(x >= 8.0 && x <= 256.0)) return bad("invalid value '" + v + "' for '--flip-ppd <X>'\n  [8 ... 256]");
+            metrics.flip_ppd = x;
+            flip_values_given = true;
+        }
+        else if (a == "--flip-map") {
+            if (!value(metrics.flip_map) || metrics.flip_map.empty()) return bad("a value is required for '--flip-map <PREFIX>' but none was supplied");
+            flip_values_given = true;
+        }
         else if (a == "--cambi-ref") { metrics.cambi_ref = true; cambi_values_given = true; }
         else if (a == "--xpsnr-fps") {
             std::string v;
@@ -274,6 +293,11 @@ int main(int argc, char **argv)
     if (pos.size() != 2) return bad("the following required arguments were not provided:\n  <REFERENCE>\n  <DISTORTED>");
     if (scene_values_given && !metrics.scenes) return bad("'--scene-threshold <X>' and '--scene-bins <N>' belong to '--scenes'");
     if (cambi_values_given && !metrics.cambi) return bad("'--cambi-window <N>', '--cambi-topk <X>' and '--cambi-ref' belong to '-m cambi'");
+    if (flip_values_given && !metrics.flip) return bad("'--flip-ppd <X>' and '--flip-map <PREFIX>' belong to '-m flip'");
+    if (metrics.flip) { // FLIP, like CAMBI, runs on one device in the batched loop
+        const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
+        if (why) { log_line(L_ERROR, kTarget, std::string("-m flip does not run with ") + why); return EXIT_FAILURE; }
+    }
     if (metrics.cambi) { // CAMBI, like VIF and ADM, runs on one device in the batched loop
         const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
         if (why) { log_line(L_ERROR, kTarget, std::string("-m cambi does not run with ") + why); return EXIT_FAILURE; }
@@ -556,7 +580,7 @@ int main(int argc, char **argv)
 
     std::unique_ptr<TurboMetrics> turbo;
     try {
-        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
+        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi && !metrics.flip) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
         // a source that knows its length never needs more slots than it has pairs (a single image pair: one slot, one engine)
         const size_t known = std::min(source_ref->frame_count(), source_dis->frame_count());
         if (batch == 0) batch = auto_batch(source_ref->width(), source_ref->height());

@@ -5,6 +5,8 @@
 #include "../../include/turbo_metrics_motion.h"
 #include "../../include/turbo_metrics_scene.h"
 #include "../../include/turbo_metrics_cambi.h"
+#include "../../include/turbo_metrics_flip.h"
+#include "frame_sources.hpp" // write_pfm_gray
 #include "../../include/turbo_metrics_vif.h"
 #include "../../include/turbo_metrics_adm.h"
 #include <dlfcn.h>
@@ -551,6 +553,89 @@ struct CambiRun {
     }
 };
 
+// ---- FLIP ----------------------------------------------------------------------------------------------------------
+// libturbometrics_flip.so, loaded at run time like the CAMBI library (a CLI run without -m flip never loads it).  Every kept pair of
+// 8-bit RGB pictures is handed over as TM_MEM_HOST copies and computed batch by batch in stream order; a pair's mean, min and max wait
+// in `ready` until the engine's scores of the same pair are drained.  --flip-map: every pair's FLIP map goes to PREFIX%06d.pfm, numbered
+// in the order the pairs are computed.  No history: --every is fine.
+struct FlipRun {
+    void *lib = nullptr;
+    int (*create)(tm_flip **, uint32_t, uint32_t, int, double, uint32_t) = nullptr;
+    void (*destroy)(tm_flip *) = nullptr;
+    int (*set_pair)(tm_flip *, uint32_t, const void *, size_t, const void *, size_t, int) = nullptr;
+    int (*compute_async)(tm_flip *, uint32_t) = nullptr;
+    int (*sync)(tm_flip *) = nullptr;
+    int (*get)(tm_flip *, uint32_t, uint32_t, tm_flip_frame *) = nullptr;
+    int (*get_map)(tm_flip *, uint32_t, int, float *, size_t) = nullptr;
+    tm_flip *s = nullptr;
+    uint32_t w, h, batch, filled = 0;
+    double ppd;
+    std::string map_prefix;
+    size_t written = 0;
+    std::vector<tm_flip_frame> out;
+    std::vector<float> map;
+    std::deque<std::array<double, 3>> ready;
+
+    FlipRun(uint32_t w_, uint32_t h_, uint32_t batch_, double ppd_, std::string prefix) : w(w_), h(h_), batch(batch_), ppd(ppd_), map_prefix(std::move(prefix))
+    {
+        const char *path = getenv("TM_FLIP_LIB");
+        lib = dlopen(path ? path : "libturbometrics_flip.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("-m flip needs libturbometrics_flip.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_flip_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_flip_destroy");
+        set_pair = (decltype(set_pair))dlsym(lib, "tm_flip_set_pair");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_flip_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_flip_sync");
+        get = (decltype(get))dlsym(lib, "tm_flip_get");
+        get_map = (decltype(get_map))dlsym(lib, "tm_flip_get_map");
+        if (!create || !destroy || !set_pair || !compute_async || !sync || !get || !get_map)
+            throw std::runtime_error("libturbometrics_flip.so does not export include/turbo_metrics_flip.h");
+    }
+    ~FlipRun()
+    {
+        if (s) destroy(s);
+        if (lib) dlclose(lib);
+    }
+    void push(const HwFrame &r, const HwFrame &d)
+    {
+        if (r.kind != HwFrame::Npp8 || d.kind != HwFrame::Npp8)
+            throw std::runtime_error("flip needs 8-bit RGB images (PNG, PPM) on both sides, not YUV or deeper pictures");
+        if (!s) {
+            const int rc = create(&s, w, h, TM_FLIP_RGB8, ppd, batch);
+            if (rc == TM_ERR_UNSUPPORTED) throw std::runtime_error("flip takes pictures of at most 2^31 samples and a --flip-ppd of 8 to 74.04 (a filter radius of at most 10)");
+            chk(rc, "tm_flip_create");
+        }
+        if (r.device != d.device) throw std::runtime_error("flip: one picture of a pair is in device memory and the other is not");
+        chk(set_pair(s, filled, r.data, r.pitch, d.data, d.pitch, r.device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_flip_set_pair");
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(s, filled), "tm_flip_compute_async");
+        chk(sync(s), "tm_flip_sync");
+        out.resize(filled);
+        chk(get(s, 0, filled, out.data()), "tm_flip_get");
+        for (uint32_t i = 0; i < filled; ++i) {
+            ready.push_back({out[i].mean, out[i].min, out[i].max});
+            if (map_prefix.empty()) continue;
+            map.resize((size_t)w * h);
+            chk(get_map(s, i, TM_FLIP_MAP, map.data(), (size_t)w * sizeof(float)), "tm_flip_get_map");
+            char num[32];
+            snprintf(num, sizeof num, "%06zu.pfm", written++);
+            write_pfm_gray(map_prefix + num, w, h, map.data());
+        }
+        filled = 0;
+    }
+    std::array<double, 3> pop()
+    {
+        if (ready.empty()) throw std::logic_error("flip: a pair's result is missing");
+        const std::array<double, 3> v = ready.front();
+        ready.pop_front();
+        return v;
+    }
+};
+
 // ---- VIF -----------------------------------------------------------------------------------------------------------
 // libturbometrics_vif.so, loaded at run time like the XPSNR and motion libraries (a CLI run without -m vif never loads it).  The lumas
 // of every kept pair are handed over as TM_MEM_HOST copies and computed batch by batch in stream order; a pair's five scores wait in
@@ -746,7 +831,8 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
     if (metrics_.scenes) sc_ = std::make_unique<SceneRun>(w_, h_, batch_, metrics_.scene_bins, metrics_.scene_threshold);
     if (metrics_.cambi) cb_ = std::make_unique<CambiRun>(w_, h_, batch_, metrics_.cambi_window, metrics_.cambi_topk);
     if (metrics_.cambi && metrics_.cambi_ref) cbr_ = std::make_unique<CambiRun>(w_, h_, batch_, metrics_.cambi_window, metrics_.cambi_topk);
-    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
+    if (metrics_.flip) fl_ = std::make_unique<FlipRun>(w_, h_, batch_, metrics_.flip_ppd, metrics_.flip_map);
+    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -1039,6 +1125,9 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         for (auto &v : s_cb) v.emplace();
     if (cbr_)
         for (auto &v : s_cbr) v.emplace();
+    std::optional<std::vector<double>> s_fl[3]; // flip, flip_min, flip_max
+    if (fl_)
+        for (auto &v : s_fl) v.emplace();
     std::optional<FrameScores> held;
     auto emit = [&](const FrameScores &r) {
         if (on_frame) on_frame(r);
@@ -1092,6 +1181,11 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
                 r.cambi_ref = v[5];
                 for (int k = 0; k < 6; ++k) s_cbr[k]->push_back(v[k]);
             }
+            if (fl_) {
+                const std::array<double, 3> v = fl_->pop();
+                r.flip = v[0]; r.flip_min = v[1]; r.flip_max = v[2];
+                for (int k = 0; k < 3; ++k) s_fl[k]->push_back(v[k]);
+            }
             if (mo_) {
                 r.motion = mo_->pop();
                 if (held) {
@@ -1116,6 +1210,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (sc_) sc_->flush();
         if (cb_) cb_->flush();
         if (cbr_) cbr_->flush();
+        if (fl_) fl_->flush();
         in_flight[i] = true;
     };
 
@@ -1189,6 +1284,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (sc_) sc_->push(fref);
         if (cb_) cb_->push(fdis);
         if (cbr_) cbr_->push(fref);
+        if (fl_) fl_->push(fref, fdis);
         if (eng_[cur]) {
             set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
             set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
@@ -1227,7 +1323,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_))
         throw NoFramesSelected();
     if (xp_) {
         std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
@@ -1259,6 +1355,11 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     if (cbr_) {
         for (int k = 0; k < 5; ++k) res.cambi_ref_scale[k] = MetricAggregate::from(std::move(*s_cbr[k]));
         res.cambi_ref = MetricAggregate::from(std::move(*s_cbr[5]));
+    }
+    if (fl_) {
+        res.flip = MetricAggregate::from(std::move(*s_fl[0]));
+        res.flip_min = MetricAggregate::from(std::move(*s_fl[1]));
+        res.flip_max = MetricAggregate::from(std::move(*s_fl[2]));
     }
     if (s_psnr) res.psnr = MetricAggregate::from(std::move(*s_psnr));
     if (s_ssim) res.ssim = MetricAggregate::from(std::move(*s_ssim));

@@ -47,6 +47,11 @@ struct Metrics {
     bool cambi = false, cambi_ref = false;
     uint32_t cambi_window = 0;
     double cambi_topk = 0.6;
+    // LDR-FLIP of pairs of 8-bit RGB pictures (include/turbo_metrics_flip.h, libturbometrics_flip.so): the CLI's -m flip, --flip-ppd (0: the
+    // library's default) and --flip-map (a prefix: every pair's map as PREFIX%06d.pfm); not an engine metric
+    bool flip = false;
+    double flip_ppd = 0.0;
+    std::string flip_map;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -86,6 +91,7 @@ struct MetricsResults {
     std::vector<size_t> scene_starts;                  // the frame indices at which a scene begins: 0 and every cut
     std::optional<MetricAggregate> cambi, cambi_scale[5];         // -m cambi: the distorted stream; their means are the sequence scores
     std::optional<MetricAggregate> cambi_ref, cambi_ref_scale[5]; // --cambi-ref: the reference stream
+    std::optional<MetricAggregate> flip, flip_min, flip_max;      // -m flip: every pair's mean, smallest and largest map value
 };
 
 struct MetricsStats {
@@ -112,6 +118,7 @@ struct FrameScores {
     std::optional<double> scene_score;
     std::optional<bool> scene_cut;
     std::optional<double> cambi, cambi_scale[5], cambi_ref, cambi_ref_scale[5];
+    std::optional<double> flip, flip_min, flip_max;
 };
 
 // ---- colour metadata (H.273 code points the reference understands, codec-bitstream/src/lib.rs:98-248) ----------
@@ -304,6 +311,7 @@ private:
     std::unique_ptr<struct VifRun> vf_;                       // metrics_.vif: the VIF library's state (likewise; no history)
     std::unique_ptr<struct AdmRun> ad_;                       // metrics_.adm: the ADM library's state (likewise; no history)
     std::unique_ptr<struct CambiRun> cb_, cbr_;               // metrics_.cambi / cambi_ref: the CAMBI library's state per stream (likewise; no history)
+    std::unique_ptr<struct FlipRun> fl_;                      // metrics_.flip: the FLIP library's state (likewise; no history)
     std::unique_ptr<struct SceneRun> sc_;                     // metrics_.scenes: the reference stream's previous histogram (likewise)
     std::unique_ptr<struct MotionRun> mo_;                    // metrics_.motion: the reference stream's motion state (likewise)
     bool full_sums_ = false;                                  // settings replayed on an engine that is created later
