@@ -47,6 +47,7 @@ void usage(std::ostream &os)
           "  <DISTORTED>  Distorted media. Use `-` to read from stdin\n\n"
           "Options:\n"
           "  -m, --metrics <METRICS>    Select the metrics to compute [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr]\n"
+          "                             [further values, each described below: vif, adm, cambi, flip, psnr-yuv, ssim-yuv]\n"
           "                             and vif: VMAF's VIF of the luma planes, four scales (YUV inputs; runs beside the others or alone)\n"
           "                             and adm: VMAF's ADM of the luma planes, adm2 and four scales (likewise)\n"
           "      --every <EVERY>        Only compute metrics every few frames [default: 0]\n"
@@ -79,6 +80,12 @@ void usage(std::ostream &os)
           "                             flip_min and flip_max, after all other columns; alone or beside the other -m values\n"
           "      --flip-ppd <X>         pixels per degree of the viewing condition, 8 ... 256; above 74.04 the run ends with an error (with -m flip) [default: 67.02]\n"
           "      --flip-map <PREFIX>    write every pair's FLIP map as a one-channel PFM, PREFIX000000.pfm, PREFIX000001.pfm, ... (with -m flip)\n"
+          "  -m psnr-yuv                PSNR per plane on the coded samples of 4:2:0 YUV pairs, as ffmpeg's psnr filter and libvmaf print it: psnr_y, psnr_u,\n"
+          "                             psnr_v, psnr_avg, after all other columns; the sequence values come from the summed squared error\n"
+          "  -m ssim-yuv                the SSIM of x264 and ffmpeg's ssim filter per plane of 4:2:0 YUV pairs: ssim_y, ssim_u, ssim_v, ssim_all, after all\n"
+          "                             other columns; the sequence values are the means over the frames; both run alone or beside the other -m values\n"
+          "      --psnr-yuv-cap         cap every PSNR at libvmaf's 6 * depth + 12 dB instead of printing inf (with -m psnr-yuv)\n"
+          "      --ssim-yuv-map <PREFIX>  write every pair's luma SSIM window map as a one-channel PFM, PREFIX000000.pfm, ... (with -m ssim-yuv)\n"
           "      --cambi-window <N>     side of the window the banding is looked for in, 3 ... 127 (with -m cambi) [default: 63 * width / 3840, at least 3]\n"
           "      --cambi-topk <X>       share of the largest c-values a scale's score averages, 0 < X <= 1 (with -m cambi) [default: 0.6]\n"
           "      --cambi-ref            also print cambi_ref and cambi_ref_scale0 .. cambi_ref_scale4 of the REFERENCE stream (with -m cambi)\n"
@@ -148,6 +155,7 @@ int main(int argc, char **argv)
     uint32_t batch = 0 /* 0: chosen from the picture size */, device = 0, devices = 1, ranks = 0 /* 0: not asked for */, in_flight_pairs = 2;
     uint32_t xpsnr_fps_num = 0, xpsnr_fps_den = 1; // --xpsnr-fps (0: not given)
     bool pipeline = true, full_sums = false, in_flight_given = false, scene_values_given = false, cambi_values_given = false, flip_values_given = false;
+    bool psnr_yuv_values_given = false, ssim_yuv_values_given = false;
     enum class Loop { Batched, Reference, Deferred } loop = Loop::Batched;
     std::vector<std::pair<int, long long>> tune;
 
@@ -184,7 +192,9 @@ int main(int argc, char **argv)
             else if (s == "adm") metrics.adm = true;
             else if (s == "cambi") metrics.cambi = true;
             else if (s == "flip") metrics.flip = true;
-            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2]");
+            else if (s == "psnr-yuv") metrics.psnr_yuv = true;
+            else if (s == "ssim-yuv") metrics.ssim_yuv = true;
+            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv]");
         } else if (a.rfind("-m", 0) == 0 && a.size() > 2 && a[1] == 'm') { // -mpsnr
             const std::string s = a.substr(2);
             if (s == "psnr") metrics.psnr = true; else if (s == "ssim") metrics.ssim = true; else if (s == "msssim") metrics.msssim = true;
@@ -194,7 +204,9 @@ int main(int argc, char **argv)
             else if (s == "adm") metrics.adm = true;
             else if (s == "cambi") metrics.cambi = true;
             else if (s == "flip") metrics.flip = true;
-            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'");
+            else if (s == "psnr-yuv") metrics.psnr_yuv = true;
+            else if (s == "ssim-yuv") metrics.ssim_yuv = true;
+            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv]");
         } else if (a == "--every") { if (!u32(opts.every)) return bad("invalid value for '--every <EVERY>'"); }
         else if (a == "--skip") { if (!u32(opts.skip)) return bad("invalid value for '--skip <SKIP>'"); }
         else if (a == "--skip-ref") { if (!u32(opts.skip_ref)) return bad("invalid value for '--skip-ref <SKIP_REF>'"); }
@@ -262,6 +274,11 @@ int main(int argc, char **argv)
             metrics.flip_ppd = x;
             flip_values_given = true;
         }
+        else if (a == "--psnr-yuv-cap") { metrics.psnr_yuv_cap = true; psnr_yuv_values_given = true; }
+        else if (a == "--ssim-yuv-map") {
+            if (!value(metrics.ssim_yuv_map) || metrics.ssim_yuv_map.empty()) return bad("a value is required for '--ssim-yuv-map <PREFIX>' but none was supplied");
+            ssim_yuv_values_given = true;
+        }
         else if (a == "--flip-map") {
             if (!value(metrics.flip_map) || metrics.flip_map.empty()) return bad("a value is required for '--flip-map <PREFIX>' but none was supplied");
             flip_values_given = true;
@@ -294,6 +311,12 @@ int main(int argc, char **argv)
     if (scene_values_given && !metrics.scenes) return bad("'--scene-threshold <X>' and '--scene-bins <N>' belong to '--scenes'");
     if (cambi_values_given && !metrics.cambi) return bad("'--cambi-window <N>', '--cambi-topk <X>' and '--cambi-ref' belong to '-m cambi'");
     if (flip_values_given && !metrics.flip) return bad("'--flip-ppd <X>' and '--flip-map <PREFIX>' belong to '-m flip'");
+    if (psnr_yuv_values_given && !metrics.psnr_yuv) return bad("'--psnr-yuv-cap' belongs to '-m psnr-yuv'");
+    if (ssim_yuv_values_given && !metrics.ssim_yuv) return bad("'--ssim-yuv-map <PREFIX>' belongs to '-m ssim-yuv'");
+    if (metrics.psnr_yuv || metrics.ssim_yuv) { // like FLIP: one device, the batched loop
+        const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
+        if (why) { log_line(L_ERROR, kTarget, std::string("-m psnr-yuv / ssim-yuv do not run with ") + why); return EXIT_FAILURE; }
+    }
     if (metrics.flip) { // FLIP, like CAMBI, runs on one device in the batched loop
         const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
         if (why) { log_line(L_ERROR, kTarget, std::string("-m flip does not run with ") + why); return EXIT_FAILURE; }
@@ -580,7 +603,7 @@ int main(int argc, char **argv)
 
     std::unique_ptr<TurboMetrics> turbo;
     try {
-        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi && !metrics.flip) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
+        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi && !metrics.flip && !metrics.psnr_yuv && !metrics.ssim_yuv) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
         // a source that knows its length never needs more slots than it has pairs (a single image pair: one slot, one engine)
         const size_t known = std::min(source_ref->frame_count(), source_dis->frame_count());
         if (batch == 0) batch = auto_batch(source_ref->width(), source_ref->height());

@@ -29,7 +29,7 @@ std::vector<Named> stat_fields(const Stats &s)
 }
 
 void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os, bool xpsnr = false, bool motion = false, bool vif = false, bool adm = false,
-                bool scene = false, bool cambi = false, bool cambi_ref = false, bool flip = false)
+                bool scene = false, bool cambi = false, bool cambi_ref = false, bool flip = false, bool psnr_yuv = false, bool ssim_yuv = false)
 {
     bool first = true;
     auto put = [&](bool on, const char *n) { if (on) { os << (first ? "" : ",") << n; first = false; } };
@@ -42,6 +42,7 @@ void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os,
     for (const char *n : {"cambi", "cambi_scale0", "cambi_scale1", "cambi_scale2", "cambi_scale3", "cambi_scale4"}) put(cambi, n);
     for (const char *n : {"cambi_ref", "cambi_ref_scale0", "cambi_ref_scale1", "cambi_ref_scale2", "cambi_ref_scale3", "cambi_ref_scale4"}) put(cambi_ref, n);
     put(flip, "flip"); put(flip, "flip_min"); put(flip, "flip_max");
+    for (int k = 0; k < 8; ++k) put(k < 4 ? psnr_yuv : ssim_yuv, kYuvNames[k]);
     if (first) os << "\"\""; // csv::Writer writes an empty record as ""
     os << "\n";
 }
@@ -52,7 +53,7 @@ void csv_row(const std::optional<double> &a, const std::optional<double> &b, con
              const std::optional<double> &mo2 = std::nullopt, const std::optional<double> *vif5 = nullptr,
              const std::optional<double> *adm5 = nullptr, const std::optional<double> &scene_score = std::nullopt,
              const std::optional<bool> &scene_cut = std::nullopt, const std::optional<double> *cambi6 = nullptr,
-             const std::optional<double> *cambi_ref6 = nullptr, const std::optional<double> *flip3 = nullptr)
+             const std::optional<double> *cambi_ref6 = nullptr, const std::optional<double> *flip3 = nullptr, const std::optional<double> *yuv8 = nullptr)
 {
     bool first = true;
     auto put = [&](const std::optional<double> &v) { if (v) { os << (first ? "" : ",") << display(*v); first = false; } };
@@ -69,6 +70,8 @@ void csv_row(const std::optional<double> &a, const std::optional<double> &b, con
         for (int k = 0; k < 6; ++k) put(cambi_ref6[k]);
     if (flip3)
         for (int k = 0; k < 3; ++k) put(flip3[k]);
+    if (yuv8)
+        for (int k = 0; k < 8; ++k) put(yuv8[k]);
     if (first) os << "\"\"";
     os << "\n";
 }
@@ -106,6 +109,7 @@ std::string frame_scores_json(const FrameScores &r)
     put("cambi_ref", r.cambi_ref);
     for (int k = 0; k < 5; ++k) put(rn[k], r.cambi_ref_scale[k]);
     put("flip", r.flip); put("flip_min", r.flip_min); put("flip_max", r.flip_max);
+    for (int k = 0; k < 8; ++k) put(kYuvNames[k], r.yuv[k]);
     return s + "}";
 }
 
@@ -135,7 +139,7 @@ std::string stats_json(const Stats &s, int indent, bool pretty)
 
 void output_prepare(Output o, const Metrics &m, std::ostream &os)
 {
-    if (o == Output::CSV) csv_header(m.psnr, m.ssim, m.msssim, m.ssimulacra2, os, m.xpsnr, m.motion, m.vif, m.adm, m.scenes, m.cambi, m.cambi && m.cambi_ref, m.flip);
+    if (o == Output::CSV) csv_header(m.psnr, m.ssim, m.msssim, m.ssimulacra2, os, m.xpsnr, m.motion, m.vif, m.adm, m.scenes, m.cambi, m.cambi && m.cambi_ref, m.flip, m.psnr_yuv, m.ssim_yuv);
 }
 
 void output_single_score(Output o, const FrameScores &r, std::ostream &os)
@@ -147,7 +151,7 @@ void output_single_score(Output o, const FrameScores &r, std::ostream &os)
         const std::optional<double> c6[6] = {r.cambi, r.cambi_scale[0], r.cambi_scale[1], r.cambi_scale[2], r.cambi_scale[3], r.cambi_scale[4]};
         const std::optional<double> r6[6] = {r.cambi_ref, r.cambi_ref_scale[0], r.cambi_ref_scale[1], r.cambi_ref_scale[2], r.cambi_ref_scale[3], r.cambi_ref_scale[4]};
         const std::optional<double> f3[3] = {r.flip, r.flip_min, r.flip_max};
-        csv_row(r.psnr, r.ssim, r.msssim, r.ssimulacra2, os, r.xpsnr_y, r.xpsnr_u, r.xpsnr_v, r.motion, r.motion2, v5, a5, r.scene_score, r.scene_cut, c6, r6, f3);
+        csv_row(r.psnr, r.ssim, r.msssim, r.ssimulacra2, os, r.xpsnr_y, r.xpsnr_u, r.xpsnr_v, r.motion, r.motion2, v5, a5, r.scene_score, r.scene_cut, c6, r6, f3, r.yuv);
     }
 }
 
@@ -193,6 +197,16 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
             os << "FLIP_MIN: " << stats_debug_pretty(r.flip_min->stats) << "\n";
             os << "FLIP_MAX: " << stats_debug_pretty(r.flip_max->stats) << "\n";
         }
+        for (int g = 0; g < 2; ++g) { // psnr_y .. psnr_avg, then ssim_y .. ssim_all, each with its sequence line
+            if (!r.yuv[4 * g]) continue;
+            for (int k = 4 * g; k < 4 * g + 4; ++k) {
+                std::string n = kYuvNames[k];
+                for (char &c : n) c = (char)toupper((unsigned char)c);
+                os << n << ": " << stats_debug_pretty(r.yuv[k]->stats) << "\n";
+            }
+            os << (g ? "SSIM-YUV (sequence): y " : "PSNR-YUV (sequence): y ") << debug(*r.yuv[4 * g]->sequence) << ", u " << debug(*r.yuv[4 * g + 1]->sequence)
+               << ", v " << debug(*r.yuv[4 * g + 2]->sequence) << (g ? ", all " : ", avg ") << debug(*r.yuv[4 * g + 3]->sequence) << "\n";
+        }
         break;
     case Output::Json: { // serde_json::to_string_pretty: two-space indent, `"key": value`
         os << "{\n  \"frame_count\": " << r.frame_count;
@@ -222,6 +236,7 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
             for (int k = 0; k < 5; ++k) put(rn[k], r.cambi_ref_scale[k]);
         }
         put("flip", r.flip); put("flip_min", r.flip_min); put("flip_max", r.flip_max);
+        for (int k = 0; k < 8; ++k) put(kYuvNames[k], r.yuv[k]);
         os << "\n}\n";
         break;
     }
@@ -263,11 +278,12 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
             for (int k = 0; k < 5; ++k) put(names[k], r.cambi_ref_scale[k]->stats);
         }
         if (r.flip) { put("flip", r.flip->stats); put("flip_min", r.flip_min->stats); put("flip_max", r.flip_max->stats); }
+        for (int k = 0; k < 8; ++k) put_x(kYuvNames[k], r.yuv[k]);
         os << "}\n";
         break;
     }
     case Output::CSV:
-        csv_header((bool)r.psnr, (bool)r.ssim, (bool)r.msssim, (bool)r.ssimulacra2, os, (bool)r.xpsnr_y, (bool)r.motion, (bool)r.vif, (bool)r.adm2, (bool)r.scene_score, (bool)r.cambi, (bool)r.cambi_ref, (bool)r.flip);
+        csv_header((bool)r.psnr, (bool)r.ssim, (bool)r.msssim, (bool)r.ssimulacra2, os, (bool)r.xpsnr_y, (bool)r.motion, (bool)r.vif, (bool)r.adm2, (bool)r.scene_score, (bool)r.cambi, (bool)r.cambi_ref, (bool)r.flip, (bool)r.yuv[0], (bool)r.yuv[4]);
         for (size_t i = 0, starts = 0; i < r.frame_count; ++i) {
             auto at = [&](const std::optional<MetricAggregate> &a) { return a ? std::optional<double>(a->scores[i]) : std::nullopt; };
             const std::optional<double> v5[5] = {at(r.vif_scale[0]), at(r.vif_scale[1]), at(r.vif_scale[2]), at(r.vif_scale[3]), at(r.vif)};
@@ -275,8 +291,9 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
             const std::optional<double> c6[6] = {at(r.cambi), at(r.cambi_scale[0]), at(r.cambi_scale[1]), at(r.cambi_scale[2]), at(r.cambi_scale[3]), at(r.cambi_scale[4])};
             const std::optional<double> r6[6] = {at(r.cambi_ref), at(r.cambi_ref_scale[0]), at(r.cambi_ref_scale[1]), at(r.cambi_ref_scale[2]), at(r.cambi_ref_scale[3]), at(r.cambi_ref_scale[4])};
             const std::optional<double> f3[3] = {at(r.flip), at(r.flip_min), at(r.flip_max)};
+            const std::optional<double> y8[8] = {at(r.yuv[0]), at(r.yuv[1]), at(r.yuv[2]), at(r.yuv[3]), at(r.yuv[4]), at(r.yuv[5]), at(r.yuv[6]), at(r.yuv[7])};
             csv_row(at(r.psnr), at(r.ssim), at(r.msssim), at(r.ssimulacra2), os, at(r.xpsnr_y), at(r.xpsnr_u), at(r.xpsnr_v), at(r.motion), at(r.motion2), v5, a5,
-                    at(r.scene_score), r.scene_score ? std::optional<bool>(i > 0 && starts < r.scene_starts.size() && r.scene_starts[starts] == i) : std::nullopt, c6, r6, f3);
+                    at(r.scene_score), r.scene_score ? std::optional<bool>(i > 0 && starts < r.scene_starts.size() && r.scene_starts[starts] == i) : std::nullopt, c6, r6, f3, y8);
             if (starts < r.scene_starts.size() && r.scene_starts[starts] == i) ++starts; // (frame 0 starts the first scene and is no cut)
         }
         break;

@@ -6,6 +6,7 @@
 #include "../../include/turbo_metrics_scene.h"
 #include "../../include/turbo_metrics_cambi.h"
 #include "../../include/turbo_metrics_flip.h"
+#include "../../include/turbo_metrics_yuv.h"
 #include "frame_sources.hpp" // write_pfm_gray
 #include "../../include/turbo_metrics_vif.h"
 #include "../../include/turbo_metrics_adm.h"
@@ -636,6 +637,144 @@ struct FlipRun {
     }
 };
 
+// ---- plane-wise YUV PSNR / SSIM --------------------------------------------------------------------------------------
+// libturbometrics_yuv.so, loaded at run time like the XPSNR library (a CLI run without -m psnr-yuv / -m ssim-yuv never loads it).  Pairs are
+// handed over as -m xpsnr hands them over and computed batch by batch in stream order; a pair's eight values (kYuvNames) wait in `ready`
+// until the engine's scores of the same pair are drained.  The sequence values: PSNR from the summed SSE over the summed sample counts,
+// SSIM as the mean over the frames.  --ssim-yuv-map: every pair's luma map goes to PREFIX%06d.pfm, numbered in the order the pairs are
+// computed.  No history: --every is fine.
+const char *const kYuvNames[8] = {"psnr_y", "psnr_u", "psnr_v", "psnr_avg", "ssim_y", "ssim_u", "ssim_v", "ssim_all"};
+
+struct YuvRun {
+    void *lib = nullptr;
+    int (*create)(tm_yuv **, uint32_t, uint32_t, int, uint32_t, uint32_t) = nullptr;
+    void (*destroy)(tm_yuv *) = nullptr;
+    int (*set_frame)(tm_yuv *, uint32_t, int, const void *, const void *, const void *, size_t, size_t, int) = nullptr;
+    int (*compute_async)(tm_yuv *, uint32_t) = nullptr;
+    int (*sync)(tm_yuv *) = nullptr;
+    int (*get)(tm_yuv *, uint32_t, uint32_t, tm_yuv_frame *) = nullptr;
+    int (*get_map)(tm_yuv *, uint32_t, int, float *, size_t) = nullptr;
+    double (*psnr)(uint64_t, uint64_t, uint32_t, double) = nullptr;
+    double (*ssim_all)(const double *, uint32_t, uint32_t) = nullptr;
+    int (*map_size)(uint32_t, uint32_t, int, uint32_t *, uint32_t *) = nullptr;
+    tm_yuv *x = nullptr;
+    uint32_t w, h, batch;
+    bool use_cap;
+    std::string map_prefix;
+    int layout = -1;
+    uint32_t bits = 8, filled = 0;
+    size_t written = 0;
+    std::vector<float> map;
+    std::deque<std::array<double, 8>> ready;
+    uint64_t sum_sse[3] = {0, 0, 0}, frames = 0;
+    double sum_ssim[4] = {0, 0, 0, 0};
+
+    YuvRun(uint32_t w_, uint32_t h_, uint32_t batch_, bool cap, std::string prefix) : w(w_), h(h_), batch(batch_), use_cap(cap), map_prefix(std::move(prefix))
+    {
+        const char *path = getenv("TM_YUV_LIB");
+        lib = dlopen(path ? path : "libturbometrics_yuv.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("-m psnr-yuv / ssim-yuv need libturbometrics_yuv.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_yuv_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_yuv_destroy");
+        set_frame = (decltype(set_frame))dlsym(lib, "tm_yuv_set_frame");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_yuv_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_yuv_sync");
+        get = (decltype(get))dlsym(lib, "tm_yuv_get");
+        get_map = (decltype(get_map))dlsym(lib, "tm_yuv_get_ssim_map");
+        psnr = (decltype(psnr))dlsym(lib, "tm_yuv_psnr");
+        ssim_all = (decltype(ssim_all))dlsym(lib, "tm_yuv_ssim_all");
+        map_size = (decltype(map_size))dlsym(lib, "tm_yuv_map_size");
+        if (!create || !destroy || !set_frame || !compute_async || !sync || !get || !get_map || !psnr || !ssim_all || !map_size)
+            throw std::runtime_error("libturbometrics_yuv.so does not export include/turbo_metrics_yuv.h");
+    }
+    ~YuvRun()
+    {
+        if (x) destroy(x);
+        if (lib) dlclose(lib);
+    }
+    static void layout_of(const HwFrame &f, int &layout, uint32_t &bits)
+    {
+        switch (f.kind) {
+        case HwFrame::NvDecNV12: layout = TM_YUV_NV12; bits = 8; return;
+        case HwFrame::NvDecP016: layout = TM_YUV_P016; bits = 10; return;
+        case HwFrame::Planar420: layout = TM_YUV_I420; bits = (uint32_t)f.bits; return;
+        case HwFrame::Planar420P10: layout = TM_YUV_I420P10_PACKED; bits = 10; return;
+        default: throw std::runtime_error("psnr-yuv / ssim-yuv need 4:2:0 YUV input");
+        }
+    }
+    uint64_t samples(int c) const { return c ? (uint64_t)((w + 1) / 2) * ((h + 1) / 2) : (uint64_t)w * h; }
+    double cap() const { return use_cap ? 6.0 * bits + 12.0 : 0.0; }
+    void push(const HwFrame &r, const HwFrame &d)
+    {
+        int lr, ld;
+        uint32_t br, bd;
+        layout_of(r, lr, br);
+        layout_of(d, ld, bd);
+        if (lr != ld || br != bd) throw std::runtime_error("psnr-yuv / ssim-yuv need reference and distorted in the same YUV layout and bit depth");
+        if (!x) {
+            layout = lr; bits = br;
+            const int rc = create(&x, w, h, layout, bits, batch);
+            if (rc == TM_ERR_UNSUPPORTED) throw std::runtime_error("psnr-yuv / ssim-yuv take pictures of 16 x 16 to 32768 x 32768 samples");
+            chk(rc, "tm_yuv_create");
+        } else if (lr != layout || br != bits) {
+            throw std::runtime_error("psnr-yuv / ssim-yuv: the YUV layout changed inside the stream");
+        }
+        const bool bi = layout == TM_YUV_NV12 || layout == TM_YUV_P016;
+        int side = TM_SIDE_REF;
+        for (const HwFrame *f : {&r, &d}) {
+            chk(set_frame(x, filled, side, f->data, bi ? f->uv : f->u, bi ? nullptr : f->v, f->pitch, bi ? f->pitch : f->pitch_uv,
+                          f->device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_yuv_set_frame");
+            side = TM_SIDE_DIS;
+        }
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(x, filled), "tm_yuv_compute_async");
+        chk(sync(x), "tm_yuv_sync");
+        std::vector<tm_yuv_frame> out(filled);
+        chk(get(x, 0, filled, out.data()), "tm_yuv_get");
+        for (uint32_t i = 0; i < filled; ++i) {
+            const tm_yuv_frame &f = out[i];
+            std::array<double, 8> v;
+            for (int c = 0; c < 3; ++c) {
+                v[c] = psnr(f.sse[c], samples(c), bits, cap());
+                v[4 + c] = f.ssim[c];
+                sum_sse[c] += f.sse[c];
+            }
+            v[3] = psnr(f.sse[0] + f.sse[1] + f.sse[2], samples(0) + 2 * samples(1), bits, cap());
+            v[7] = ssim_all(f.ssim, w, h);
+            for (int k = 0; k < 4; ++k) sum_ssim[k] += v[4 + k];
+            ready.push_back(v);
+            ++frames;
+            if (map_prefix.empty()) continue;
+            uint32_t mw = 0, mh = 0;
+            chk(map_size(w, h, 0, &mw, &mh), "tm_yuv_map_size");
+            map.resize((size_t)mw * mh);
+            chk(get_map(x, i, 0, map.data(), (size_t)mw * sizeof(float)), "tm_yuv_get_ssim_map");
+            char num[32];
+            snprintf(num, sizeof num, "%06zu.pfm", written++);
+            write_pfm_gray(map_prefix + num, mw, mh, map.data());
+        }
+        filled = 0;
+    }
+    std::array<double, 8> pop()
+    {
+        if (ready.empty()) throw std::logic_error("psnr-yuv / ssim-yuv: a pair's result is missing");
+        const std::array<double, 8> v = ready.front();
+        ready.pop_front();
+        return v;
+    }
+    // the sequence value of column k (kYuvNames)
+    double sequence_score(int k) const
+    {
+        if (k < 3) return psnr(sum_sse[k], samples(k) * frames, bits, cap());
+        if (k == 3) return psnr(sum_sse[0] + sum_sse[1] + sum_sse[2], (samples(0) + 2 * samples(1)) * frames, bits, cap());
+        return sum_ssim[k - 4] / (double)frames;
+    }
+};
+
 // ---- VIF -----------------------------------------------------------------------------------------------------------
 // libturbometrics_vif.so, loaded at run time like the XPSNR and motion libraries (a CLI run without -m vif never loads it).  The lumas
 // of every kept pair are handed over as TM_MEM_HOST copies and computed batch by batch in stream order; a pair's five scores wait in
@@ -832,7 +971,8 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
     if (metrics_.cambi) cb_ = std::make_unique<CambiRun>(w_, h_, batch_, metrics_.cambi_window, metrics_.cambi_topk);
     if (metrics_.cambi && metrics_.cambi_ref) cbr_ = std::make_unique<CambiRun>(w_, h_, batch_, metrics_.cambi_window, metrics_.cambi_topk);
     if (metrics_.flip) fl_ = std::make_unique<FlipRun>(w_, h_, batch_, metrics_.flip_ppd, metrics_.flip_map);
-    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
+    if (metrics_.psnr_yuv || metrics_.ssim_yuv) yv_ = std::make_unique<YuvRun>(w_, h_, batch_, metrics_.psnr_yuv_cap, metrics_.ssim_yuv_map);
+    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -1128,6 +1268,9 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     std::optional<std::vector<double>> s_fl[3]; // flip, flip_min, flip_max
     if (fl_)
         for (auto &v : s_fl) v.emplace();
+    std::optional<std::vector<double>> s_yv[8]; // kYuvNames: [0 .. 3] with psnr-yuv, [4 .. 7] with ssim-yuv
+    for (int k = 0; k < 8; ++k)
+        if (k < 4 ? metrics_.psnr_yuv : metrics_.ssim_yuv) s_yv[k].emplace();
     std::optional<FrameScores> held;
     auto emit = [&](const FrameScores &r) {
         if (on_frame) on_frame(r);
@@ -1186,6 +1329,11 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
                 r.flip = v[0]; r.flip_min = v[1]; r.flip_max = v[2];
                 for (int k = 0; k < 3; ++k) s_fl[k]->push_back(v[k]);
             }
+            if (yv_) {
+                const std::array<double, 8> v = yv_->pop();
+                for (int k = 0; k < 8; ++k)
+                    if (s_yv[k]) { r.yuv[k] = v[k]; s_yv[k]->push_back(v[k]); }
+            }
             if (mo_) {
                 r.motion = mo_->pop();
                 if (held) {
@@ -1211,6 +1359,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (cb_) cb_->flush();
         if (cbr_) cbr_->flush();
         if (fl_) fl_->flush();
+        if (yv_) yv_->flush();
         in_flight[i] = true;
     };
 
@@ -1285,6 +1434,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (cb_) cb_->push(fdis);
         if (cbr_) cbr_->push(fref);
         if (fl_) fl_->push(fref, fdis);
+        if (yv_) yv_->push(fref, fdis);
         if (eng_[cur]) {
             set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
             set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
@@ -1323,7 +1473,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_))
         throw NoFramesSelected();
     if (xp_) {
         std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
@@ -1361,6 +1511,11 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         res.flip_min = MetricAggregate::from(std::move(*s_fl[1]));
         res.flip_max = MetricAggregate::from(std::move(*s_fl[2]));
     }
+    for (int k = 0; k < 8; ++k)
+        if (s_yv[k]) {
+            res.yuv[k] = MetricAggregate::from(std::move(*s_yv[k]));
+            res.yuv[k]->sequence = yv_->sequence_score(k);
+        }
     if (s_psnr) res.psnr = MetricAggregate::from(std::move(*s_psnr));
     if (s_ssim) res.ssim = MetricAggregate::from(std::move(*s_ssim));
     if (s_msssim) res.msssim = MetricAggregate::from(std::move(*s_msssim));

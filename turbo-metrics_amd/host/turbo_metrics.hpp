@@ -52,6 +52,10 @@ struct Metrics {
     bool flip = false;
     double flip_ppd = 0.0;
     std::string flip_map;
+    // plane-wise PSNR and x264 / ffmpeg SSIM of 4:2:0 pairs (include/turbo_metrics_yuv.h, libturbometrics_yuv.so): the CLI's -m psnr-yuv and
+    // -m ssim-yuv, --psnr-yuv-cap (libvmaf's 6 D + 12) and --ssim-yuv-map (a prefix: every pair's luma map as PREFIX%06d.pfm); not engine metrics
+    bool psnr_yuv = false, ssim_yuv = false, psnr_yuv_cap = false;
+    std::string ssim_yuv_map;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -92,6 +96,9 @@ struct MetricsResults {
     std::optional<MetricAggregate> cambi, cambi_scale[5];         // -m cambi: the distorted stream; their means are the sequence scores
     std::optional<MetricAggregate> cambi_ref, cambi_ref_scale[5]; // --cambi-ref: the reference stream
     std::optional<MetricAggregate> flip, flip_min, flip_max;      // -m flip: every pair's mean, smallest and largest map value
+    // -m psnr-yuv: [0 .. 3] psnr_y, psnr_u, psnr_v, psnr_avg (sequence: from the summed SSE); -m ssim-yuv: [4 .. 7] ssim_y, ssim_u, ssim_v,
+    // ssim_all (sequence: the mean over the frames); names: kYuvNames
+    std::optional<MetricAggregate> yuv[8];
 };
 
 struct MetricsStats {
@@ -119,7 +126,10 @@ struct FrameScores {
     std::optional<bool> scene_cut;
     std::optional<double> cambi, cambi_scale[5], cambi_ref, cambi_ref_scale[5];
     std::optional<double> flip, flip_min, flip_max;
+    std::optional<double> yuv[8]; // kYuvNames
 };
+
+extern const char *const kYuvNames[8];
 
 // ---- colour metadata (H.273 code points the reference understands, codec-bitstream/src/lib.rs:98-248) ----------
 enum class ColourPrimaries { Invalid, Unspecified, Unsupported, BT709, BT601_525, BT601_625 };
@@ -311,6 +321,7 @@ private:
     std::unique_ptr<struct VifRun> vf_;                       // metrics_.vif: the VIF library's state (likewise; no history)
     std::unique_ptr<struct AdmRun> ad_;                       // metrics_.adm: the ADM library's state (likewise; no history)
     std::unique_ptr<struct CambiRun> cb_, cbr_;               // metrics_.cambi / cambi_ref: the CAMBI library's state per stream (likewise; no history)
+    std::unique_ptr<struct YuvRun> yv_;                       // metrics_.psnr_yuv / ssim_yuv: the YUV PSNR / SSIM library's state (likewise; no history)
     std::unique_ptr<struct FlipRun> fl_;                      // metrics_.flip: the FLIP library's state (likewise; no history)
     std::unique_ptr<struct SceneRun> sc_;                     // metrics_.scenes: the reference stream's previous histogram (likewise)
     std::unique_ptr<struct MotionRun> mo_;                    // metrics_.motion: the reference stream's motion state (likewise)
