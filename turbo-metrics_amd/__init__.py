@@ -12,6 +12,7 @@ C ABI) with a host-side mirror of the reference's operator interface.
   cambi   -- ctypes binding of include/turbo_metrics_cambi.h (libturbometrics_cambi.so): Cambi, VMAF's banding index of one stream
   flip    -- ctypes binding of include/turbo_metrics_flip.h (libturbometrics_flip.so): Flip, the LDR-FLIP difference map of picture pairs
   yuv     -- ctypes binding of include/turbo_metrics_yuv.h (libturbometrics_yuv.so): Yuv, plane-wise PSNR and x264 / ffmpeg SSIM of 4:2:0 pairs
+  hvs     -- ctypes binding of include/turbo_metrics_hvs.h (libturbometrics_hvs.so): Hvs, PSNR-HVS and PSNR-HVS-M of the lumas of frame pairs
 
 There is no CPU implementation in this package: without the HIP library (or without a gfx950 GPU)
 the operators raise.
@@ -33,3 +34,5 @@ from . import flip  # noqa: F401,E402
 from .flip import Flip, FlipFrame  # noqa: F401,E402
 from . import yuv  # noqa: F401,E402
 from .yuv import Yuv, YuvFrame  # noqa: F401,E402
+from . import hvs  # noqa: F401,E402
+from .hvs import Hvs, HvsFrame  # noqa: F401,E402

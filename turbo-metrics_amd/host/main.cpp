@@ -48,6 +48,7 @@ void usage(std::ostream &os)
           "Options:\n"
           "  -m, --metrics <METRICS>    Select the metrics to compute [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr]\n"
           "                             [further values, each described below: vif, adm, cambi, flip, psnr-yuv, ssim-yuv]\n"
+          "                             [and: psnr-hvs, psnr-hvs-m]\n"
           "                             and vif: VMAF's VIF of the luma planes, four scales (YUV inputs; runs beside the others or alone)\n"
           "                             and adm: VMAF's ADM of the luma planes, adm2 and four scales (likewise)\n"
           "      --every <EVERY>        Only compute metrics every few frames [default: 0]\n"
@@ -84,6 +85,10 @@ void usage(std::ostream &os)
           "                             psnr_v, psnr_avg, after all other columns; the sequence values come from the summed squared error\n"
           "  -m ssim-yuv                the SSIM of x264 and ffmpeg's ssim filter per plane of 4:2:0 YUV pairs: ssim_y, ssim_u, ssim_v, ssim_all, after all\n"
           "                             other columns; the sequence values are the means over the frames; both run alone or beside the other -m values\n"
+          "  -m psnr-hvs                PSNR-HVS of the luma planes of YUV pairs: the 8x8 DCT coefficients of the difference weighted by a contrast\n"
+          "                             sensitivity table, non-overlapping blocks (not libvmaf's variant): psnr_hvs, after all other columns\n"
+          "  -m psnr-hvs-m              PSNR-HVS-M: the same after contrast masking by the two pictures' blocks: psnr_hvs_m, after all other columns; the\n"
+          "                             sequence values come from the summed weighted error; both run alone or beside the other -m values\n"
           "      --psnr-yuv-cap         cap every PSNR at libvmaf's 6 * depth + 12 dB instead of printing inf (with -m psnr-yuv)\n"
           "      --ssim-yuv-map <PREFIX>  write every pair's luma SSIM window map as a one-channel PFM, PREFIX000000.pfm, ... (with -m ssim-yuv)\n"
           "      --cambi-window <N>     side of the window the banding is looked for in, 3 ... 127 (with -m cambi) [default: 63 * width / 3840, at least 3]\n"
@@ -194,7 +199,9 @@ int main(int argc, char **argv)
             else if (s == "flip") metrics.flip = true;
             else if (s == "psnr-yuv") metrics.psnr_yuv = true;
             else if (s == "ssim-yuv") metrics.ssim_yuv = true;
-            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv]");
+            else if (s == "psnr-hvs") metrics.psnr_hvs = true;
+            else if (s == "psnr-hvs-m") metrics.psnr_hvs_m = true;
+            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv, psnr-hvs, psnr-hvs-m]");
         } else if (a.rfind("-m", 0) == 0 && a.size() > 2 && a[1] == 'm') { // -mpsnr
             const std::string s = a.substr(2);
             if (s == "psnr") metrics.psnr = true; else if (s == "ssim") metrics.ssim = true; else if (s == "msssim") metrics.msssim = true;
@@ -206,7 +213,9 @@ int main(int argc, char **argv)
             else if (s == "flip") metrics.flip = true;
             else if (s == "psnr-yuv") metrics.psnr_yuv = true;
             else if (s == "ssim-yuv") metrics.ssim_yuv = true;
-            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv]");
+            else if (s == "psnr-hvs") metrics.psnr_hvs = true;
+            else if (s == "psnr-hvs-m") metrics.psnr_hvs_m = true;
+            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv, psnr-hvs, psnr-hvs-m]");
         } else if (a == "--every") { if (!u32(opts.every)) return bad("invalid value for '--every <EVERY>'"); }
         else if (a == "--skip") { if (!u32(opts.skip)) return bad("invalid value for '--skip <SKIP>'"); }
         else if (a == "--skip-ref") { if (!u32(opts.skip_ref)) return bad("invalid value for '--skip-ref <SKIP_REF>'"); }
@@ -316,6 +325,10 @@ int main(int argc, char **argv)
     if (metrics.psnr_yuv || metrics.ssim_yuv) { // like FLIP: one device, the batched loop
         const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
         if (why) { log_line(L_ERROR, kTarget, std::string("-m psnr-yuv / ssim-yuv do not run with ") + why); return EXIT_FAILURE; }
+    }
+    if (metrics.psnr_hvs || metrics.psnr_hvs_m) { // like VIF: one device, the batched loop
+        const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
+        if (why) { log_line(L_ERROR, kTarget, std::string("-m psnr-hvs / psnr-hvs-m do not run with ") + why); return EXIT_FAILURE; }
     }
     if (metrics.flip) { // FLIP, like CAMBI, runs on one device in the batched loop
         const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
@@ -603,7 +616,7 @@ int main(int argc, char **argv)
 
     std::unique_ptr<TurboMetrics> turbo;
     try {
-        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi && !metrics.flip && !metrics.psnr_yuv && !metrics.ssim_yuv) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
+        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi && !metrics.flip && !metrics.psnr_yuv && !metrics.ssim_yuv && !metrics.psnr_hvs && !metrics.psnr_hvs_m) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
         // a source that knows its length never needs more slots than it has pairs (a single image pair: one slot, one engine)
         const size_t known = std::min(source_ref->frame_count(), source_dis->frame_count());
         if (batch == 0) batch = auto_batch(source_ref->width(), source_ref->height());

@@ -7,6 +7,7 @@
 #include "../../include/turbo_metrics_cambi.h"
 #include "../../include/turbo_metrics_flip.h"
 #include "../../include/turbo_metrics_yuv.h"
+#include "../../include/turbo_metrics_hvs.h"
 #include "frame_sources.hpp" // write_pfm_gray
 #include "../../include/turbo_metrics_vif.h"
 #include "../../include/turbo_metrics_adm.h"
@@ -775,6 +776,105 @@ struct YuvRun {
     }
 };
 
+// ---- PSNR-HVS / PSNR-HVS-M ---------------------------------------------------------------------------------------------
+// libturbometrics_hvs.so, loaded at run time like the VIF library (a CLI run without -m psnr-hvs / -m psnr-hvs-m never loads it).  The lumas
+// of every kept pair are handed over as -m vif hands them over and computed batch by batch in stream order; a pair's two values
+// (kHvsNames) wait in `ready` until the engine's scores of the same pair are drained.  The sequence values: the PSNR of the summed S
+// over the summed number of blocks.  No history: --every is fine.
+const char *const kHvsNames[2] = {"psnr_hvs", "psnr_hvs_m"};
+
+struct HvsRun {
+    void *lib = nullptr;
+    int (*create)(tm_hvs **, uint32_t, uint32_t, int, uint32_t, uint32_t) = nullptr;
+    void (*destroy)(tm_hvs *) = nullptr;
+    int (*set_pair)(tm_hvs *, uint32_t, const void *, const void *, size_t, size_t, int) = nullptr;
+    int (*compute_async)(tm_hvs *, uint32_t) = nullptr;
+    int (*sync)(tm_hvs *) = nullptr;
+    int (*get)(tm_hvs *, uint32_t, uint32_t, tm_hvs_frame *) = nullptr;
+    double (*psnr)(double, uint64_t, uint32_t) = nullptr;
+    tm_hvs *v = nullptr;
+    uint32_t w, h, batch;
+    int layout = -1;
+    uint32_t bits = 8, filled = 0;
+    std::deque<std::array<double, 2>> ready;
+    double sum_s[2] = {0.0, 0.0};
+    uint64_t sum_blocks = 0;
+
+    HvsRun(uint32_t w_, uint32_t h_, uint32_t batch_) : w(w_), h(h_), batch(batch_)
+    {
+        const char *path = getenv("TM_HVS_LIB");
+        lib = dlopen(path ? path : "libturbometrics_hvs.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("-m psnr-hvs / psnr-hvs-m need libturbometrics_hvs.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_hvs_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_hvs_destroy");
+        set_pair = (decltype(set_pair))dlsym(lib, "tm_hvs_set_pair");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_hvs_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_hvs_sync");
+        get = (decltype(get))dlsym(lib, "tm_hvs_get");
+        psnr = (decltype(psnr))dlsym(lib, "tm_hvs_psnr");
+        if (!create || !destroy || !set_pair || !compute_async || !sync || !get || !psnr) {
+            dlclose(lib); // the destructor does not run for an object whose constructor throws
+            throw std::runtime_error("libturbometrics_hvs.so does not export include/turbo_metrics_hvs.h");
+        }
+    }
+    ~HvsRun()
+    {
+        if (v) destroy(v);
+        if (lib) dlclose(lib);
+    }
+    static void layout_of(const HwFrame &f, int &l, uint32_t &b)
+    {
+        switch (f.kind) {
+        case HwFrame::NvDecNV12: l = TM_HVS_Y8; b = 8; return;
+        case HwFrame::NvDecP016: l = TM_HVS_Y16_MSB; b = 10; return;
+        case HwFrame::Planar420: b = (uint32_t)f.bits; l = b == 8 ? TM_HVS_Y8 : TM_HVS_Y16_LOW; return;
+        case HwFrame::Planar420P10: l = TM_HVS_Y10_PACKED; b = 10; return;
+        default: throw std::runtime_error("psnr-hvs / psnr-hvs-m need YUV input (Y4M, raw planar YUV or decoded video), not RGB images");
+        }
+    }
+    void push(const HwFrame &r, const HwFrame &d)
+    {
+        int lr, ld;
+        uint32_t br, bd;
+        layout_of(r, lr, br);
+        layout_of(d, ld, bd);
+        if (lr != ld || br != bd || r.device != d.device) throw std::runtime_error("psnr-hvs / psnr-hvs-m need reference and distorted in the same YUV layout and bit depth");
+        if (!v) {
+            layout = lr; bits = br;
+            const int rc = create(&v, w, h, layout, bits, batch);
+            if (rc == TM_ERR_UNSUPPORTED) throw std::runtime_error("psnr-hvs / psnr-hvs-m take pictures of 8 x 8 to 32768 x 32768 samples");
+            chk(rc, "tm_hvs_create");
+        } else if (lr != layout || br != bits) {
+            throw std::runtime_error("psnr-hvs / psnr-hvs-m: the YUV layout changed inside the stream");
+        }
+        chk(set_pair(v, filled, r.data, d.data, r.pitch, d.pitch, r.device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_hvs_set_pair");
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(v, filled), "tm_hvs_compute_async");
+        chk(sync(v), "tm_hvs_sync");
+        std::vector<tm_hvs_frame> out(filled);
+        chk(get(v, 0, filled, out.data()), "tm_hvs_get");
+        for (const tm_hvs_frame &f : out) {
+            ready.push_back({psnr(f.s_hvs, f.blocks, bits), psnr(f.s_hvsm, f.blocks, bits)});
+            sum_s[0] += f.s_hvs; sum_s[1] += f.s_hvsm;
+            sum_blocks += f.blocks;
+        }
+        filled = 0;
+    }
+    std::array<double, 2> pop()
+    {
+        if (ready.empty()) throw std::logic_error("psnr-hvs / psnr-hvs-m: a pair's result is missing");
+        const std::array<double, 2> s = ready.front();
+        ready.pop_front();
+        return s;
+    }
+    // the sequence value of column k (kHvsNames)
+    double sequence_score(int k) const { return psnr(sum_s[k], sum_blocks, bits); }
+};
+
 // ---- VIF -----------------------------------------------------------------------------------------------------------
 // libturbometrics_vif.so, loaded at run time like the XPSNR and motion libraries (a CLI run without -m vif never loads it).  The lumas
 // of every kept pair are handed over as TM_MEM_HOST copies and computed batch by batch in stream order; a pair's five scores wait in
@@ -972,7 +1072,8 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
     if (metrics_.cambi && metrics_.cambi_ref) cbr_ = std::make_unique<CambiRun>(w_, h_, batch_, metrics_.cambi_window, metrics_.cambi_topk);
     if (metrics_.flip) fl_ = std::make_unique<FlipRun>(w_, h_, batch_, metrics_.flip_ppd, metrics_.flip_map);
     if (metrics_.psnr_yuv || metrics_.ssim_yuv) yv_ = std::make_unique<YuvRun>(w_, h_, batch_, metrics_.psnr_yuv_cap, metrics_.ssim_yuv_map);
-    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
+    if (metrics_.psnr_hvs || metrics_.psnr_hvs_m) hv_ = std::make_unique<HvsRun>(w_, h_, batch_);
+    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_ || hv_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -1271,6 +1372,9 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     std::optional<std::vector<double>> s_yv[8]; // kYuvNames: [0 .. 3] with psnr-yuv, [4 .. 7] with ssim-yuv
     for (int k = 0; k < 8; ++k)
         if (k < 4 ? metrics_.psnr_yuv : metrics_.ssim_yuv) s_yv[k].emplace();
+    std::optional<std::vector<double>> s_hv[2]; // kHvsNames
+    if (metrics_.psnr_hvs) s_hv[0].emplace();
+    if (metrics_.psnr_hvs_m) s_hv[1].emplace();
     std::optional<FrameScores> held;
     auto emit = [&](const FrameScores &r) {
         if (on_frame) on_frame(r);
@@ -1334,6 +1438,11 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
                 for (int k = 0; k < 8; ++k)
                     if (s_yv[k]) { r.yuv[k] = v[k]; s_yv[k]->push_back(v[k]); }
             }
+            if (hv_) {
+                const std::array<double, 2> v = hv_->pop();
+                for (int k = 0; k < 2; ++k)
+                    if (s_hv[k]) { r.hvs[k] = v[k]; s_hv[k]->push_back(v[k]); }
+            }
             if (mo_) {
                 r.motion = mo_->pop();
                 if (held) {
@@ -1360,6 +1469,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (cbr_) cbr_->flush();
         if (fl_) fl_->flush();
         if (yv_) yv_->flush();
+        if (hv_) hv_->flush();
         in_flight[i] = true;
     };
 
@@ -1435,6 +1545,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (cbr_) cbr_->push(fref);
         if (fl_) fl_->push(fref, fdis);
         if (yv_) yv_->push(fref, fdis);
+        if (hv_) hv_->push(fref, fdis);
         if (eng_[cur]) {
             set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
             set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
@@ -1473,7 +1584,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_ || hv_))
         throw NoFramesSelected();
     if (xp_) {
         std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
@@ -1515,6 +1626,11 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (s_yv[k]) {
             res.yuv[k] = MetricAggregate::from(std::move(*s_yv[k]));
             res.yuv[k]->sequence = yv_->sequence_score(k);
+        }
+    for (int k = 0; k < 2; ++k)
+        if (s_hv[k]) {
+            res.hvs[k] = MetricAggregate::from(std::move(*s_hv[k]));
+            res.hvs[k]->sequence = hv_->sequence_score(k);
         }
     if (s_psnr) res.psnr = MetricAggregate::from(std::move(*s_psnr));
     if (s_ssim) res.ssim = MetricAggregate::from(std::move(*s_ssim));

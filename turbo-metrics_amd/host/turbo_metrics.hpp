@@ -56,6 +56,9 @@ struct Metrics {
     // -m ssim-yuv, --psnr-yuv-cap (libvmaf's 6 D + 12) and --ssim-yuv-map (a prefix: every pair's luma map as PREFIX%06d.pfm); not engine metrics
     bool psnr_yuv = false, ssim_yuv = false, psnr_yuv_cap = false;
     std::string ssim_yuv_map;
+    // PSNR-HVS and PSNR-HVS-M of the luma planes (include/turbo_metrics_hvs.h, libturbometrics_hvs.so): the CLI's -m psnr-hvs and -m psnr-hvs-m;
+    // not engine metrics
+    bool psnr_hvs = false, psnr_hvs_m = false;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -99,6 +102,8 @@ struct MetricsResults {
     // -m psnr-yuv: [0 .. 3] psnr_y, psnr_u, psnr_v, psnr_avg (sequence: from the summed SSE); -m ssim-yuv: [4 .. 7] ssim_y, ssim_u, ssim_v,
     // ssim_all (sequence: the mean over the frames); names: kYuvNames
     std::optional<MetricAggregate> yuv[8];
+    // -m psnr-hvs: [0] psnr_hvs; -m psnr-hvs-m: [1] psnr_hvs_m (sequence: from the summed S over the summed Num); names: kHvsNames
+    std::optional<MetricAggregate> hvs[2];
 };
 
 struct MetricsStats {
@@ -127,9 +132,11 @@ struct FrameScores {
     std::optional<double> cambi, cambi_scale[5], cambi_ref, cambi_ref_scale[5];
     std::optional<double> flip, flip_min, flip_max;
     std::optional<double> yuv[8]; // kYuvNames
+    std::optional<double> hvs[2]; // kHvsNames
 };
 
 extern const char *const kYuvNames[8];
+extern const char *const kHvsNames[2];
 
 // ---- colour metadata (H.273 code points the reference understands, codec-bitstream/src/lib.rs:98-248) ----------
 enum class ColourPrimaries { Invalid, Unspecified, Unsupported, BT709, BT601_525, BT601_625 };
@@ -322,6 +329,7 @@ private:
     std::unique_ptr<struct AdmRun> ad_;                       // metrics_.adm: the ADM library's state (likewise; no history)
     std::unique_ptr<struct CambiRun> cb_, cbr_;               // metrics_.cambi / cambi_ref: the CAMBI library's state per stream (likewise; no history)
     std::unique_ptr<struct YuvRun> yv_;                       // metrics_.psnr_yuv / ssim_yuv: the YUV PSNR / SSIM library's state (likewise; no history)
+    std::unique_ptr<struct HvsRun> hv_;                       // metrics_.psnr_hvs / psnr_hvs_m: the PSNR-HVS library's state (likewise; no history)
     std::unique_ptr<struct FlipRun> fl_;                      // metrics_.flip: the FLIP library's state (likewise; no history)
     std::unique_ptr<struct SceneRun> sc_;                     // metrics_.scenes: the reference stream's previous histogram (likewise)
     std::unique_ptr<struct MotionRun> mo_;                    // metrics_.motion: the reference stream's motion state (likewise)
