@@ -49,6 +49,7 @@ void usage(std::ostream &os)
           "  -m, --metrics <METRICS>    Select the metrics to compute [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr]\n"
           "                             [further values, each described below: vif, adm, cambi, flip, psnr-yuv, ssim-yuv]\n"
           "                             [and: psnr-hvs, psnr-hvs-m]\n"
+          "                             [and: ciede2000]\n"
           "                             and vif: VMAF's VIF of the luma planes, four scales (YUV inputs; runs beside the others or alone)\n"
           "                             and adm: VMAF's ADM of the luma planes, adm2 and four scales (likewise)\n"
           "      --every <EVERY>        Only compute metrics every few frames [default: 0]\n"
@@ -89,6 +90,12 @@ void usage(std::ostream &os)
           "                             sensitivity table, non-overlapping blocks (not libvmaf's variant): psnr_hvs, after all other columns\n"
           "  -m psnr-hvs-m              PSNR-HVS-M: the same after contrast masking by the two pictures' blocks: psnr_hvs_m, after all other columns; the\n"
           "                             sequence values come from the summed weighted error; both run alone or beside the other -m values\n"
+          "  -m ciede2000               CIEDE2000 of 4:2:0 YUV pairs: the colour difference dE00 (Sharma, Wu, Dalal 2005) of every luma position, chroma taken\n"
+          "                             without interpolation, Lab from limited-range Y'CbCr through the sRGB curve with the matrix of --matrix-coefficients:\n"
+          "                             ciede2000 = min(45 - 20 log10(mean dE00), 100) and ciede2000_de, the mean dE00, after all other columns; the sequence\n"
+          "                             values come from the summed dE00; alone or beside the other -m values\n"
+          "      --ciede-libvmaf        the matrix and the factors kL, kC, kH = 0.65, 1, 4 libvmaf's ciede feature is recalled to use (with -m ciede2000)\n"
+          "      --ciede-map <PREFIX>   write every pair's dE00 map as a one-channel PFM, PREFIX000000.pfm, PREFIX000001.pfm, ... (with -m ciede2000)\n"
           "      --psnr-yuv-cap         cap every PSNR at libvmaf's 6 * depth + 12 dB instead of printing inf (with -m psnr-yuv)\n"
           "      --ssim-yuv-map <PREFIX>  write every pair's luma SSIM window map as a one-channel PFM, PREFIX000000.pfm, ... (with -m ssim-yuv)\n"
           "      --cambi-window <N>     side of the window the banding is looked for in, 3 ... 127 (with -m cambi) [default: 63 * width / 3840, at least 3]\n"
@@ -160,7 +167,7 @@ int main(int argc, char **argv)
     uint32_t batch = 0 /* 0: chosen from the picture size */, device = 0, devices = 1, ranks = 0 /* 0: not asked for */, in_flight_pairs = 2;
     uint32_t xpsnr_fps_num = 0, xpsnr_fps_den = 1; // --xpsnr-fps (0: not given)
     bool pipeline = true, full_sums = false, in_flight_given = false, scene_values_given = false, cambi_values_given = false, flip_values_given = false;
-    bool psnr_yuv_values_given = false, ssim_yuv_values_given = false;
+    bool psnr_yuv_values_given = false, ssim_yuv_values_given = false, ciede_values_given = false;
     enum class Loop { Batched, Reference, Deferred } loop = Loop::Batched;
     std::vector<std::pair<int, long long>> tune;
 
@@ -201,7 +208,8 @@ int main(int argc, char **argv)
             else if (s == "ssim-yuv") metrics.ssim_yuv = true;
             else if (s == "psnr-hvs") metrics.psnr_hvs = true;
             else if (s == "psnr-hvs-m") metrics.psnr_hvs_m = true;
-            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv, psnr-hvs, psnr-hvs-m]");
+            else if (s == "ciede2000") metrics.ciede = true;
+            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv, psnr-hvs, psnr-hvs-m] [and: ciede2000]");
         } else if (a.rfind("-m", 0) == 0 && a.size() > 2 && a[1] == 'm') { // -mpsnr
             const std::string s = a.substr(2);
             if (s == "psnr") metrics.psnr = true; else if (s == "ssim") metrics.ssim = true; else if (s == "msssim") metrics.msssim = true;
@@ -215,7 +223,8 @@ int main(int argc, char **argv)
             else if (s == "ssim-yuv") metrics.ssim_yuv = true;
             else if (s == "psnr-hvs") metrics.psnr_hvs = true;
             else if (s == "psnr-hvs-m") metrics.psnr_hvs_m = true;
-            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv, psnr-hvs, psnr-hvs-m]");
+            else if (s == "ciede2000") metrics.ciede = true;
+            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv, psnr-hvs, psnr-hvs-m] [and: ciede2000]");
         } else if (a == "--every") { if (!u32(opts.every)) return bad("invalid value for '--every <EVERY>'"); }
         else if (a == "--skip") { if (!u32(opts.skip)) return bad("invalid value for '--skip <SKIP>'"); }
         else if (a == "--skip-ref") { if (!u32(opts.skip_ref)) return bad("invalid value for '--skip-ref <SKIP_REF>'"); }
@@ -292,6 +301,11 @@ int main(int argc, char **argv)
             if (!value(metrics.flip_map) || metrics.flip_map.empty()) return bad("a value is required for '--flip-map <PREFIX>' but none was supplied");
             flip_values_given = true;
         }
+        else if (a == "--ciede-libvmaf") { metrics.ciede_libvmaf = true; ciede_values_given = true; }
+        else if (a == "--ciede-map") {
+            if (!value(metrics.ciede_map) || metrics.ciede_map.empty()) return bad("a value is required for '--ciede-map <PREFIX>' but none was supplied");
+            ciede_values_given = true;
+        }
         else if (a == "--cambi-ref") { metrics.cambi_ref = true; cambi_values_given = true; }
         else if (a == "--xpsnr-fps") {
             std::string v;
@@ -325,6 +339,11 @@ int main(int argc, char **argv)
     if (metrics.psnr_yuv || metrics.ssim_yuv) { // like FLIP: one device, the batched loop
         const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
         if (why) { log_line(L_ERROR, kTarget, std::string("-m psnr-yuv / ssim-yuv do not run with ") + why); return EXIT_FAILURE; }
+    }
+    if (ciede_values_given && !metrics.ciede) return bad("'--ciede-libvmaf' and '--ciede-map <PREFIX>' belong to '-m ciede2000'");
+    if (metrics.ciede) { // like -m psnr-yuv: one device, the batched loop
+        const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
+        if (why) { log_line(L_ERROR, kTarget, std::string("-m ciede2000 does not run with ") + why); return EXIT_FAILURE; }
     }
     if (metrics.psnr_hvs || metrics.psnr_hvs_m) { // like VIF: one device, the batched loop
         const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
@@ -616,7 +635,7 @@ int main(int argc, char **argv)
 
     std::unique_ptr<TurboMetrics> turbo;
     try {
-        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi && !metrics.flip && !metrics.psnr_yuv && !metrics.ssim_yuv && !metrics.psnr_hvs && !metrics.psnr_hvs_m) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
+        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi && !metrics.flip && !metrics.psnr_yuv && !metrics.ssim_yuv && !metrics.psnr_hvs && !metrics.psnr_hvs_m && !metrics.ciede) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
         // a source that knows its length never needs more slots than it has pairs (a single image pair: one slot, one engine)
         const size_t known = std::min(source_ref->frame_count(), source_dis->frame_count());
         if (batch == 0) batch = auto_batch(source_ref->width(), source_ref->height());

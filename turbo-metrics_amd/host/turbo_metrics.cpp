@@ -8,6 +8,7 @@
 #include "../../include/turbo_metrics_flip.h"
 #include "../../include/turbo_metrics_yuv.h"
 #include "../../include/turbo_metrics_hvs.h"
+#include "../../include/turbo_metrics_ciede.h"
 #include "frame_sources.hpp" // write_pfm_gray
 #include "../../include/turbo_metrics_vif.h"
 #include "../../include/turbo_metrics_adm.h"
@@ -875,6 +876,140 @@ struct HvsRun {
     double sequence_score(int k) const { return psnr(sum_s[k], sum_blocks, bits); }
 };
 
+// ---- CIEDE2000 ---------------------------------------------------------------------------------------------------------
+// libturbometrics_ciede.so, loaded at run time like the YUV library (a CLI run without -m ciede2000 never loads it).  Pairs are handed over
+// as -m psnr-yuv hands them over and computed batch by batch in stream order; a pair's two values (kCiedeNames: the score and the mean dE00)
+// wait in `ready` until the engine's scores of the same pair are drained.  The matrix comes from the streams' colour metadata (BT.709 or
+// BT.601; both streams the same), or is libvmaf's with --ciede-libvmaf, which also sets kL, kC, kH = 0.65, 1, 4.  The sequence values: from
+// the summed dE00 over the summed positions.  --ciede-map: every pair's dE00 map goes to PREFIX%06d.pfm, numbered in the order the pairs are
+// computed.  No history: --every is fine.
+const char *const kCiedeNames[2] = {"ciede2000", "ciede2000_de"};
+
+struct CiedeRun {
+    void *lib = nullptr;
+    int (*create)(tm_ciede **, uint32_t, uint32_t, int, uint32_t, int, double, double, double, int, int, uint32_t) = nullptr;
+    void (*destroy)(tm_ciede *) = nullptr;
+    int (*set_frame)(tm_ciede *, uint32_t, int, const void *, const void *, const void *, size_t, size_t, int) = nullptr;
+    int (*compute_async)(tm_ciede *, uint32_t) = nullptr;
+    int (*sync)(tm_ciede *) = nullptr;
+    int (*get)(tm_ciede *, uint32_t, uint32_t, tm_ciede_frame *) = nullptr;
+    int (*get_map)(tm_ciede *, uint32_t, float *, size_t) = nullptr;
+    double (*score)(double, uint64_t) = nullptr;
+    tm_ciede *x = nullptr;
+    uint32_t w, h, batch;
+    bool libvmaf;
+    std::string map_prefix;
+    int layout = -1, matrix = -1;
+    uint32_t bits = 8, filled = 0;
+    size_t written = 0;
+    std::vector<float> map;
+    std::deque<std::array<double, 2>> ready;
+    double sum_de = 0.0;
+    uint64_t sum_px = 0;
+
+    CiedeRun(uint32_t w_, uint32_t h_, uint32_t batch_, bool libvmaf_, std::string prefix) : w(w_), h(h_), batch(batch_), libvmaf(libvmaf_), map_prefix(std::move(prefix))
+    {
+        const char *path = getenv("TM_CIEDE_LIB");
+        lib = dlopen(path ? path : "libturbometrics_ciede.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("-m ciede2000 needs libturbometrics_ciede.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_ciede_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_ciede_destroy");
+        set_frame = (decltype(set_frame))dlsym(lib, "tm_ciede_set_frame");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_ciede_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_ciede_sync");
+        get = (decltype(get))dlsym(lib, "tm_ciede_get");
+        get_map = (decltype(get_map))dlsym(lib, "tm_ciede_get_map");
+        score = (decltype(score))dlsym(lib, "tm_ciede_score");
+        if (!create || !destroy || !set_frame || !compute_async || !sync || !get || !get_map || !score) {
+            dlclose(lib); // the destructor does not run for an object whose constructor throws
+            throw std::runtime_error("libturbometrics_ciede.so does not export include/turbo_metrics_ciede.h");
+        }
+    }
+    ~CiedeRun()
+    {
+        if (x) destroy(x);
+        if (lib) dlclose(lib);
+    }
+    static void layout_of(const HwFrame &f, int &layout, uint32_t &bits)
+    {
+        switch (f.kind) {
+        case HwFrame::NvDecNV12: layout = TM_CIEDE_NV12; bits = 8; return;
+        case HwFrame::NvDecP016: layout = TM_CIEDE_P016; bits = 10; return;
+        case HwFrame::Planar420: layout = TM_CIEDE_I420; bits = (uint32_t)f.bits; return;
+        case HwFrame::Planar420P10: layout = TM_CIEDE_I420P10_PACKED; bits = 10; return;
+        default: throw std::runtime_error("ciede2000 needs 4:2:0 YUV input (Y4M, raw planar YUV or decoded video), not RGB images");
+        }
+    }
+    // the library's matrix for a stream's colour metadata
+    using ColorInfo = TurboMetrics::ColorInfo;
+    int matrix_of(const ColorInfo &c) const
+    {
+        if (c.second == ColorRange::Full) throw std::runtime_error("ciede2000 takes limited-range YUV only");
+        if (libvmaf) return TM_CIEDE_LIBVMAF;
+        switch (c.first.mc) {
+        case MatrixCoefficients::BT709: return TM_CIEDE_BT709;
+        case MatrixCoefficients::BT601_525: case MatrixCoefficients::BT601_625: return TM_CIEDE_BT601;
+        default: throw std::runtime_error(std::string("ciede2000: not implemented: matrix coefficients ") + to_string(c.first.mc));
+        }
+    }
+    void push(const HwFrame &r, const HwFrame &d, const ColorInfo &cr, const ColorInfo &cd)
+    {
+        int lr, ld;
+        uint32_t br, bd;
+        layout_of(r, lr, br);
+        layout_of(d, ld, bd);
+        if (lr != ld || br != bd) throw std::runtime_error("ciede2000 needs reference and distorted in the same YUV layout and bit depth");
+        const int mr = matrix_of(cr), md = matrix_of(cd);
+        if (mr != md) throw std::runtime_error("ciede2000 needs reference and distorted with the same matrix coefficients");
+        if (!x) {
+            layout = lr; bits = br; matrix = mr;
+            const int rc = create(&x, w, h, layout, bits, matrix, libvmaf ? 0.65 : 1.0, 1.0, libvmaf ? 4.0 : 1.0, 0, map_prefix.empty() ? 0 : 1, batch);
+            if (rc == TM_ERR_UNSUPPORTED) throw std::runtime_error("ciede2000 takes pictures of 2 x 2 to 32768 x 32768 samples");
+            chk(rc, "tm_ciede_create");
+        } else if (lr != layout || br != bits || mr != matrix) {
+            throw std::runtime_error("ciede2000: the YUV layout or the matrix changed inside the stream");
+        }
+        const bool bi = layout == TM_CIEDE_NV12 || layout == TM_CIEDE_P016;
+        int side = TM_SIDE_REF;
+        for (const HwFrame *f : {&r, &d}) {
+            chk(set_frame(x, filled, side, f->data, bi ? f->uv : f->u, bi ? nullptr : f->v, f->pitch, bi ? f->pitch : f->pitch_uv,
+                          f->device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_ciede_set_frame");
+            side = TM_SIDE_DIS;
+        }
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(x, filled), "tm_ciede_compute_async");
+        chk(sync(x), "tm_ciede_sync");
+        std::vector<tm_ciede_frame> out(filled);
+        chk(get(x, 0, filled, out.data()), "tm_ciede_get");
+        for (uint32_t i = 0; i < filled; ++i) {
+            const tm_ciede_frame &f = out[i];
+            ready.push_back({f.score, f.de_mean});
+            sum_de += f.de_sum;
+            sum_px += f.pixels;
+            if (map_prefix.empty()) continue;
+            map.resize((size_t)w * h);
+            chk(get_map(x, i, map.data(), (size_t)w * sizeof(float)), "tm_ciede_get_map");
+            char num[32];
+            snprintf(num, sizeof num, "%06zu.pfm", written++);
+            write_pfm_gray(map_prefix + num, w, h, map.data());
+        }
+        filled = 0;
+    }
+    std::array<double, 2> pop()
+    {
+        if (ready.empty()) throw std::logic_error("ciede2000: a pair's result is missing");
+        const std::array<double, 2> v = ready.front();
+        ready.pop_front();
+        return v;
+    }
+    // the sequence value of column k (kCiedeNames)
+    double sequence_score(int k) const { return k ? sum_de / (double)sum_px : score(sum_de, sum_px); }
+};
+
 // ---- VIF -----------------------------------------------------------------------------------------------------------
 // libturbometrics_vif.so, loaded at run time like the XPSNR and motion libraries (a CLI run without -m vif never loads it).  The lumas
 // of every kept pair are handed over as TM_MEM_HOST copies and computed batch by batch in stream order; a pair's five scores wait in
@@ -1073,7 +1208,8 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
     if (metrics_.flip) fl_ = std::make_unique<FlipRun>(w_, h_, batch_, metrics_.flip_ppd, metrics_.flip_map);
     if (metrics_.psnr_yuv || metrics_.ssim_yuv) yv_ = std::make_unique<YuvRun>(w_, h_, batch_, metrics_.psnr_yuv_cap, metrics_.ssim_yuv_map);
     if (metrics_.psnr_hvs || metrics_.psnr_hvs_m) hv_ = std::make_unique<HvsRun>(w_, h_, batch_);
-    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_ || hv_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
+    if (metrics_.ciede) ci_ = std::make_unique<CiedeRun>(w_, h_, batch_, metrics_.ciede_libvmaf, metrics_.ciede_map);
+    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_ || hv_ || ci_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -1375,6 +1511,8 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     std::optional<std::vector<double>> s_hv[2]; // kHvsNames
     if (metrics_.psnr_hvs) s_hv[0].emplace();
     if (metrics_.psnr_hvs_m) s_hv[1].emplace();
+    std::optional<std::vector<double>> s_ci[2]; // kCiedeNames
+    if (metrics_.ciede) { s_ci[0].emplace(); s_ci[1].emplace(); }
     std::optional<FrameScores> held;
     auto emit = [&](const FrameScores &r) {
         if (on_frame) on_frame(r);
@@ -1443,6 +1581,10 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
                 for (int k = 0; k < 2; ++k)
                     if (s_hv[k]) { r.hvs[k] = v[k]; s_hv[k]->push_back(v[k]); }
             }
+            if (ci_) {
+                const std::array<double, 2> v = ci_->pop();
+                for (int k = 0; k < 2; ++k) { r.ciede[k] = v[k]; s_ci[k]->push_back(v[k]); }
+            }
             if (mo_) {
                 r.motion = mo_->pop();
                 if (held) {
@@ -1470,6 +1612,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (fl_) fl_->flush();
         if (yv_) yv_->flush();
         if (hv_) hv_->flush();
+        if (ci_) ci_->flush();
         in_flight[i] = true;
     };
 
@@ -1546,6 +1689,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (fl_) fl_->push(fref, fdis);
         if (yv_) yv_->push(fref, fdis);
         if (hv_) hv_->push(fref, fdis);
+        if (ci_) ci_->push(fref, fdis, cref, cdis);
         if (eng_[cur]) {
             set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
             set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
@@ -1584,7 +1728,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_ || hv_))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_ || hv_ || ci_))
         throw NoFramesSelected();
     if (xp_) {
         std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
@@ -1631,6 +1775,11 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (s_hv[k]) {
             res.hvs[k] = MetricAggregate::from(std::move(*s_hv[k]));
             res.hvs[k]->sequence = hv_->sequence_score(k);
+        }
+    for (int k = 0; k < 2; ++k)
+        if (s_ci[k]) {
+            res.ciede[k] = MetricAggregate::from(std::move(*s_ci[k]));
+            res.ciede[k]->sequence = ci_->sequence_score(k);
         }
     if (s_psnr) res.psnr = MetricAggregate::from(std::move(*s_psnr));
     if (s_ssim) res.ssim = MetricAggregate::from(std::move(*s_ssim));

@@ -59,6 +59,10 @@ struct Metrics {
     // PSNR-HVS and PSNR-HVS-M of the luma planes (include/turbo_metrics_hvs.h, libturbometrics_hvs.so): the CLI's -m psnr-hvs and -m psnr-hvs-m;
     // not engine metrics
     bool psnr_hvs = false, psnr_hvs_m = false;
+    // CIEDE2000 of 4:2:0 pairs (include/turbo_metrics_ciede.h, libturbometrics_ciede.so): the CLI's -m ciede2000, --ciede-libvmaf (the matrix and
+    // the factors libvmaf is recalled to use) and --ciede-map (a prefix: every pair's dE00 map as PREFIX%06d.pfm); not an engine metric
+    bool ciede = false, ciede_libvmaf = false;
+    std::string ciede_map;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -104,6 +108,8 @@ struct MetricsResults {
     std::optional<MetricAggregate> yuv[8];
     // -m psnr-hvs: [0] psnr_hvs; -m psnr-hvs-m: [1] psnr_hvs_m (sequence: from the summed S over the summed Num); names: kHvsNames
     std::optional<MetricAggregate> hvs[2];
+    // -m ciede2000: [0] ciede2000 (the score), [1] ciede2000_de (the mean dE00); sequence: from the summed dE00 over the summed positions; names: kCiedeNames
+    std::optional<MetricAggregate> ciede[2];
 };
 
 struct MetricsStats {
@@ -133,10 +139,12 @@ struct FrameScores {
     std::optional<double> flip, flip_min, flip_max;
     std::optional<double> yuv[8]; // kYuvNames
     std::optional<double> hvs[2]; // kHvsNames
+    std::optional<double> ciede[2]; // kCiedeNames
 };
 
 extern const char *const kYuvNames[8];
 extern const char *const kHvsNames[2];
+extern const char *const kCiedeNames[2];
 
 // ---- colour metadata (H.273 code points the reference understands, codec-bitstream/src/lib.rs:98-248) ----------
 enum class ColourPrimaries { Invalid, Unspecified, Unsupported, BT709, BT601_525, BT601_625 };
@@ -329,6 +337,7 @@ private:
     std::unique_ptr<struct AdmRun> ad_;                       // metrics_.adm: the ADM library's state (likewise; no history)
     std::unique_ptr<struct CambiRun> cb_, cbr_;               // metrics_.cambi / cambi_ref: the CAMBI library's state per stream (likewise; no history)
     std::unique_ptr<struct YuvRun> yv_;                       // metrics_.psnr_yuv / ssim_yuv: the YUV PSNR / SSIM library's state (likewise; no history)
+    std::unique_ptr<struct CiedeRun> ci_;                     // metrics_.ciede: the CIEDE2000 library's state (likewise; no history)
     std::unique_ptr<struct HvsRun> hv_;                       // metrics_.psnr_hvs / psnr_hvs_m: the PSNR-HVS library's state (likewise; no history)
     std::unique_ptr<struct FlipRun> fl_;                      // metrics_.flip: the FLIP library's state (likewise; no history)
     std::unique_ptr<struct SceneRun> sc_;                     // metrics_.scenes: the reference stream's previous histogram (likewise)
