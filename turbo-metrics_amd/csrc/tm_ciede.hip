@@ -1,5 +1,6 @@
 // tm_ciede.hip -- host side of libturbometrics_ciede.so (include/turbo_metrics_ciede.h): frame upload, the two launches per batch and
-// the host functions of the definition, in double.  Kernels: tm_ciede_kernels.h.
+// the host functions of the definition, in double.  Kernels: tm_ciede_kernels.h; the host core it shares:
+// tm_feature_host.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -10,19 +11,12 @@
 
 #include "../../include/turbo_metrics_ciede.h"
 #include "tm_ciede_kernels.h"
+#include "tm_feature_host.h"
 
 namespace {
 
 static_assert(TMC_NV12 == TM_CIEDE_NV12 && TMC_P016 == TM_CIEDE_P016 && TMC_I420 == TM_CIEDE_I420 && TMC_I420P10 == TM_CIEDE_I420P10_PACKED, "layouts");
 static_assert(TM_CIEDE_BT709 == 0 && TM_CIEDE_BT601 == 1 && TM_CIEDE_LIBVMAF == 2 && TMC_MATRICES == 3, "matrices");
-
-#define CCHK(call)                                      \
-    do {                                                \
-        if ((call) != hipSuccess) {                     \
-            (void)hipGetLastError();                    \
-            return TM_ERR_HIP;                          \
-        }                                               \
-    } while (0)
 
 const double kMatrix[TMC_MATRICES][4] = TMC_MATRIX_VALUES;
 
@@ -30,31 +24,15 @@ const double kMatrix[TMC_MATRICES][4] = TMC_MATRIX_VALUES;
 
 struct tm_ciede {
     TmCiedeGeom g;
-    uint32_t cap;
-    int device;
-    hipStream_t stream = nullptr;
+    TmFeatureHost c;                                  // have, staging: [slot][side]
     TmCiedeDesc *d_desc = nullptr, *h_desc = nullptr; // [slot][side]; h_desc is page-locked, copied at each compute
     std::vector<TmCiedeDesc> desc;                    // what set_frame wrote
-    std::vector<unsigned char> have;                  // [slot][side]: set since the last compute
-    std::vector<void *> staging;                      // [slot][side]: device copy of a host picture (lazily allocated)
     float *d_maps = nullptr;                          // want_map: [slot][h][w]: every value is written by every compute
     TmCiedeCell *d_cells = nullptr;                   // [slot][g.cells]: likewise
     TmCiedeCell *d_res = nullptr, *h_res = nullptr;   // [slot]
-    size_t bytes = 0;
-    bool pending = false;
-    uint32_t n_last = 0;
 };
 
 namespace {
-
-int dev_alloc(tm_ciede *x, void **p, size_t n)
-{
-    const hipError_t r = hipMalloc(p, n ? n : 1);
-    if (r == hipErrorOutOfMemory) { (void)hipGetLastError(); return TM_ERR_OOM; }
-    CCHK(r);
-    x->bytes += n;
-    return TM_OK;
-}
 
 // bytes of one luma / chroma row of this layout, and the number of chroma planes
 void plane_rows(const tm_ciede *x, size_t *row_y, size_t *row_c, int *nc)
@@ -158,24 +136,22 @@ int tm_ciede_create(tm_ciede **out, uint32_t w, uint32_t h, int layout, uint32_t
     if (tmc_make_geom(&g, w, h, layout, bits)) return TM_ERR_UNSUPPORTED;
     if (tmc_set_params(&g, matrix, kl, kc, kh)) return TM_ERR_INVALID_ARG;
     if (batch_capacity > 65535u) return TM_ERR_INVALID_ARG; // the slots are the launch's grid y
+    tm_ciede *x = new tm_ciede();
+    x->g = g;
+    const size_t B = batch_capacity;
     int rc;
     // ---- first device call
-    tm_ciede *x = new tm_ciede();
-    x->g = g; x->cap = batch_capacity;
-    auto fail = [&](int e) { tm_ciede_destroy(x); return e; };
-    if (hipGetDevice(&x->device) != hipSuccess) { (void)hipGetLastError(); delete x; return TM_ERR_HIP; }
-    if (hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); x->stream = nullptr; return fail(TM_ERR_HIP); }
-    const size_t B = batch_capacity;
-    if ((rc = dev_alloc(x, (void **)&x->d_desc, B * 2 * sizeof(TmCiedeDesc)))) return fail(rc);
-    if (want_map && (rc = dev_alloc(x, (void **)&x->d_maps, B * (size_t)g.w * g.h * sizeof(float)))) return fail(rc);
-    if ((rc = dev_alloc(x, (void **)&x->d_cells, B * g.cells * sizeof(TmCiedeCell)))) return fail(rc);
-    if ((rc = dev_alloc(x, (void **)&x->d_res, B * sizeof(TmCiedeCell)))) return fail(rc);
-    if (hipHostMalloc((void **)&x->h_desc, B * 2 * sizeof(TmCiedeDesc), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); x->h_desc = nullptr; return fail(TM_ERR_OOM); }
-    if (hipHostMalloc((void **)&x->h_res, B * sizeof(TmCiedeCell), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); x->h_res = nullptr; return fail(TM_ERR_OOM); }
-    x->bytes += B * 2 * sizeof(TmCiedeDesc) + B * sizeof(TmCiedeCell);
+    if ((rc = tmfh_open(&x->c, batch_capacity, B * 2, B * 2))) { delete x; return rc; }
+    if ((rc = tmfh_dev_alloc(&x->c, &x->d_desc, B * 2 * sizeof(TmCiedeDesc))) ||
+        (want_map && (rc = tmfh_dev_alloc(&x->c, &x->d_maps, B * (size_t)g.w * g.h * sizeof(float)))) ||
+        (rc = tmfh_dev_alloc(&x->c, &x->d_cells, B * g.cells * sizeof(TmCiedeCell))) ||
+        (rc = tmfh_dev_alloc(&x->c, &x->d_res, B * sizeof(TmCiedeCell))) ||
+        (rc = tmfh_pinned_alloc(&x->c, &x->h_desc, B * 2 * sizeof(TmCiedeDesc))) ||
+        (rc = tmfh_pinned_alloc(&x->c, &x->h_res, B * sizeof(TmCiedeCell)))) {
+        tm_ciede_destroy(x);
+        return rc;
+    }
     x->desc.assign(B * 2, TmCiedeDesc{});
-    x->have.assign(B * 2, 0);
-    x->staging.assign(B * 2, nullptr);
     *out = x;
     return TM_OK;
 }
@@ -183,26 +159,17 @@ int tm_ciede_create(tm_ciede **out, uint32_t w, uint32_t h, int layout, uint32_t
 void tm_ciede_destroy(tm_ciede *x)
 {
     if (!x) return;
-    if (x->stream) (void)hipStreamSynchronize(x->stream);
-    for (void *p : x->staging) if (p) (void)hipFree(p);
-    if (x->d_desc) (void)hipFree(x->d_desc);
-    if (x->d_maps) (void)hipFree(x->d_maps);
-    if (x->d_cells) (void)hipFree(x->d_cells);
-    if (x->d_res) (void)hipFree(x->d_res);
-    if (x->h_desc) (void)hipHostFree(x->h_desc);
-    if (x->h_res) (void)hipHostFree(x->h_res);
-    if (x->stream) (void)hipStreamDestroy(x->stream);
-    (void)hipGetLastError();
+    tmfh_close(&x->c, {x->d_desc, x->d_maps, x->d_cells, x->d_res}, {x->h_desc, x->h_res});
     delete x;
 }
 
-size_t tm_ciede_mem_usage(const tm_ciede *x) { return x ? x->bytes : 0; }
+size_t tm_ciede_mem_usage(const tm_ciede *x) { return x ? x->c.bytes : 0; }
 
 int tm_ciede_set_frame(tm_ciede *x, uint32_t slot, int side, const void *y, const void *u, const void *v, size_t pitch_y,
                        size_t pitch_uv, int mem)
 {
-    if (!x || slot >= x->cap || (side != TM_SIDE_REF && side != TM_SIDE_DIS) || !y || !u) return TM_ERR_INVALID_ARG;
-    if (mem != TM_MEM_HOST && mem != TM_MEM_DEVICE && mem != TM_MEM_HOST_PINNED) return TM_ERR_INVALID_ARG;
+    if (!x || slot >= x->c.cap || (side != TM_SIDE_REF && side != TM_SIDE_DIS) || !y || !u) return TM_ERR_INVALID_ARG;
+    if (!tmfh_mem_ok(mem)) return TM_ERR_INVALID_ARG;
     const TmCiedeGeom &g = x->g;
     const bool biplanar = g.layout == TM_CIEDE_NV12 || g.layout == TM_CIEDE_P016;
     if (biplanar) v = nullptr;
@@ -213,89 +180,53 @@ int tm_ciede_set_frame(tm_ciede *x, uint32_t slot, int side, const void *y, cons
     if (pitch_y < row_y || pitch_uv < row_c) return TM_ERR_INVALID_ARG;
     const size_t align = g.layout == TM_CIEDE_I420P10_PACKED ? 4 : (g.bits == 8 ? 1 : 2);
     if (((uintptr_t)y | (uintptr_t)u | (uintptr_t)v | pitch_y | pitch_uv) & (align - 1)) return TM_ERR_INVALID_ARG;
-    if (x->pending && mem != TM_MEM_DEVICE) {
-        const int rc = tm_ciede_sync(x); // the staging surface may still be read; a device surface is only noted in a host-side descriptor
-        if (rc) return rc;
-    }
-    if (hipSetDevice(x->device) != hipSuccess) { (void)hipGetLastError(); return TM_ERR_HIP; }
-    const unsigned ph = g.h, ch = g.ch;
+    int rc;
+    // not for TM_MEM_DEVICE: the staging surface may still be read; a device surface is only noted in a host-side descriptor
+    if (mem != TM_MEM_DEVICE && (rc = tmfh_sync(&x->c))) return rc;
+    TMFH_CHK(hipSetDevice(x->c.device));
     const size_t idx = (size_t)slot * 2 + side;
-    TmCiedeDesc d{};
-    if (mem == TM_MEM_DEVICE) {
-        d.p0 = y; d.p1 = u; d.p2 = v; d.pitch = pitch_y; d.pitch2 = pitch_uv;
-    } else {
-        const size_t sp_y = (row_y + 255) / 256 * 256, sp_c = (row_c + 255) / 256 * 256;
-        const size_t need = sp_y * ph + nc * sp_c * ch;
-        if (!x->staging[idx]) {
-            const int rc = dev_alloc(x, &x->staging[idx], need);
-            if (rc) return rc;
-        }
-        char *s = (char *)x->staging[idx];
-        const hipMemcpyKind k = hipMemcpyHostToDevice;
-        CCHK(hipMemcpy2DAsync(s, sp_y, y, pitch_y, row_y, ph, k, x->stream));
-        CCHK(hipMemcpy2DAsync(s + sp_y * ph, sp_c, u, pitch_uv, row_c, ch, k, x->stream));
-        if (!biplanar) CCHK(hipMemcpy2DAsync(s + sp_y * ph + sp_c * ch, sp_c, v, pitch_uv, row_c, ch, k, x->stream));
-        if (mem == TM_MEM_HOST) CCHK(hipStreamSynchronize(x->stream));
-        d.p0 = s; d.p1 = s + sp_y * ph; d.p2 = biplanar ? nullptr : s + sp_y * ph + sp_c * ch; d.pitch = sp_y; d.pitch2 = sp_c;
+    const void *p[3] = {y, u, v};
+    unsigned long long pitch[2] = {pitch_y, pitch_uv};
+    if (mem != TM_MEM_DEVICE) {
+        if ((rc = tmfh_upload_420(&x->c, idx, y, u, v, pitch_y, pitch_uv, row_y, row_c, g.h, g.ch, nc, p, pitch))) return rc;
+        if (mem == TM_MEM_HOST) TMFH_CHK(hipStreamSynchronize(x->c.stream));
     }
-    d.vec = (((uintptr_t)d.p0 | (uintptr_t)d.p1 | (uintptr_t)d.p2 | d.pitch | d.pitch2) & 15) == 0;
+    TmCiedeDesc d{};
+    d.p0 = p[0]; d.p1 = p[1]; d.p2 = p[2]; d.pitch = pitch[0]; d.pitch2 = pitch[1];
+    d.vec = tmfh_vec((uintptr_t)d.p0 | (uintptr_t)d.p1 | (uintptr_t)d.p2 | d.pitch | d.pitch2);
     x->desc[idx] = d;
-    x->have[idx] = 1;
+    x->c.have[idx] = 1;
     return TM_OK;
 }
 
 int tm_ciede_compute_async(tm_ciede *x, uint32_t n_slots)
 {
-    if (!x || n_slots == 0 || n_slots > x->cap) return TM_ERR_INVALID_ARG;
-    if (x->pending) return TM_ERR_STATE;
-    for (uint32_t i = 0; i < 2 * n_slots; ++i)
-        if (!x->have[i]) return TM_ERR_STATE;
-    if (hipSetDevice(x->device) != hipSuccess) { (void)hipGetLastError(); return TM_ERR_HIP; }
+    if (!x) return TM_ERR_INVALID_ARG;
+    const int rc = tmfh_begin(&x->c, n_slots, 2);
+    if (rc) return rc;
+    hipStream_t stream = x->c.stream;
     memcpy(x->h_desc, x->desc.data(), 2 * n_slots * sizeof(TmCiedeDesc));
-    // after the first queued operation a failure must not leave work behind that still reads the descriptors and the staging surfaces
-    // while the caller believes nothing is pending: wait for what was queued, then report
-#define CQUEUED(call)                                   \
-    do {                                                \
-        if ((call) != hipSuccess) {                     \
-            (void)hipGetLastError();                    \
-            (void)hipStreamSynchronize(x->stream);      \
-            (void)hipGetLastError();                    \
-            return TM_ERR_HIP;                          \
-        }                                               \
-    } while (0)
-    CCHK(hipMemcpyAsync(x->d_desc, x->h_desc, 2 * n_slots * sizeof(TmCiedeDesc), hipMemcpyHostToDevice, x->stream));
+    TMFH_CHK(hipMemcpyAsync(x->d_desc, x->h_desc, 2 * n_slots * sizeof(TmCiedeDesc), hipMemcpyHostToDevice, stream));
     const TmCiedeGeom g = x->g;
     const dim3 grid(g.cells, n_slots), block(TMC_THREADS);
-#define TMC_LAUNCH(L, F) k_ciede<L, F><<<grid, block, 0, x->stream>>>(g, x->d_desc, x->d_maps, x->d_cells)
+#define TMC_LAUNCH(L, F) k_ciede<L, F><<<grid, block, 0, stream>>>(g, x->d_desc, x->d_maps, x->d_cells)
     TMC_DISPATCH(g, TMC_LAUNCH);
 #undef TMC_LAUNCH
-    CQUEUED(hipGetLastError());
-    k_ciede_finish<<<dim3(n_slots), block, 0, x->stream>>>(g, x->d_cells, x->d_res);
-    CQUEUED(hipGetLastError());
-    CQUEUED(hipMemcpyAsync(x->h_res, x->d_res, n_slots * sizeof(TmCiedeCell), hipMemcpyDeviceToHost, x->stream));
-#undef CQUEUED
-    x->pending = true;
-    // every batch hands its pictures over anew: a slot not set again before the next compute is TM_ERR_STATE, not a stale picture
-    std::fill(x->have.begin(), x->have.begin() + 2 * n_slots, 0);
-    x->n_last = n_slots;
+    TMFH_CHK_QUEUED(&x->c, hipGetLastError());
+    k_ciede_finish<<<dim3(n_slots), block, 0, stream>>>(g, x->d_cells, x->d_res);
+    TMFH_CHK_QUEUED(&x->c, hipGetLastError());
+    TMFH_CHK_QUEUED(&x->c, hipMemcpyAsync(x->h_res, x->d_res, n_slots * sizeof(TmCiedeCell), hipMemcpyDeviceToHost, stream));
+    tmfh_queued(&x->c, n_slots, 2);
     return TM_OK;
 }
 
-int tm_ciede_sync(tm_ciede *x)
-{
-    if (!x) return TM_ERR_INVALID_ARG;
-    if (!x->pending) return TM_OK;
-    if (hipSetDevice(x->device) != hipSuccess) { (void)hipGetLastError(); return TM_ERR_HIP; }
-    CCHK(hipStreamSynchronize(x->stream));
-    x->pending = false;
-    return TM_OK;
-}
+int tm_ciede_sync(tm_ciede *x) { return x ? tmfh_sync(&x->c) : TM_ERR_INVALID_ARG; }
 
 int tm_ciede_get(tm_ciede *x, uint32_t first_slot, uint32_t n, tm_ciede_frame *out)
 {
     if (!x || !out) return TM_ERR_INVALID_ARG;
-    if (x->n_last == 0 || first_slot + (uint64_t)n > x->n_last) return TM_ERR_STATE;
-    const int rc = tm_ciede_sync(x);
+    if (!tmfh_in_last(&x->c, first_slot, n)) return TM_ERR_STATE;
+    const int rc = tmfh_sync(&x->c);
     if (rc) return rc;
     const uint64_t px = (uint64_t)x->g.w * x->g.h;
     for (uint32_t i = 0; i < n; ++i) {
@@ -314,13 +245,14 @@ int tm_ciede_get_map(tm_ciede *x, uint32_t slot, float *dst, size_t pitch)
     if (!x || !dst) return TM_ERR_INVALID_ARG;
     const TmCiedeGeom &g = x->g;
     if (pitch < (size_t)g.w * sizeof(float) || (pitch & 3)) return TM_ERR_INVALID_ARG;
-    if (!x->d_maps || slot >= x->n_last) return TM_ERR_STATE;
-    const int rc = tm_ciede_sync(x);
+    if (!x->d_maps || slot >= x->c.n_last) return TM_ERR_STATE;
+    const int rc = tmfh_sync(&x->c);
     if (rc) return rc;
-    if (hipSetDevice(x->device) != hipSuccess) { (void)hipGetLastError(); return TM_ERR_HIP; }
+    TMFH_CHK(hipSetDevice(x->c.device));
     const float *src = x->d_maps + (size_t)slot * g.w * g.h;
-    CCHK(hipMemcpy2D(dst, pitch, src, (size_t)g.w * sizeof(float), (size_t)g.w * sizeof(float), g.h, hipMemcpyDeviceToHost));
+    TMFH_CHK(hipMemcpy2D(dst, pitch, src, (size_t)g.w * sizeof(float), (size_t)g.w * sizeof(float), g.h, hipMemcpyDeviceToHost));
     return TM_OK;
 }
 
 } // extern "C"
+
