@@ -14,6 +14,7 @@ C ABI) with a host-side mirror of the reference's operator interface.
   yuv     -- ctypes binding of include/turbo_metrics_yuv.h (libturbometrics_yuv.so): Yuv, plane-wise PSNR and x264 / ffmpeg SSIM of 4:2:0 pairs
   hvs     -- ctypes binding of include/turbo_metrics_hvs.h (libturbometrics_hvs.so): Hvs, PSNR-HVS and PSNR-HVS-M of the lumas of frame pairs
   ciede   -- ctypes binding of include/turbo_metrics_ciede.h (libturbometrics_ciede.so): Ciede, CIEDE2000 of 4:2:0 frame pairs
+  siti    -- ctypes binding of include/turbo_metrics_siti.h (libturbometrics_siti.so): Siti, ITU-T P.910 spatial / temporal information of one stream
 
 There is no CPU implementation in this package: without the HIP library (or without a gfx950 GPU)
 the operators raise.
@@ -39,3 +40,5 @@ from . import hvs  # noqa: F401,E402
 from .hvs import Hvs, HvsFrame  # noqa: F401,E402
 from . import ciede  # noqa: F401,E402
 from .ciede import Ciede, CiedeFrame  # noqa: F401,E402
+from . import siti  # noqa: F401,E402
+from .siti import Siti, SitiFrame  # noqa: F401,E402

@@ -72,6 +72,11 @@ void usage(std::ostream &os)
           "      --color-primaries <N> --matrix-coefficients <N> --transfer-characteristics <N>   H.273 codes (1, 5, 6; 2 = by height)\n"
           "      --full-range           the YUV input is full range (unsupported by the reference and here)\n"
           "      --motion               also compute VMAF's integer motion / motion2 of the REFERENCE stream (YUV inputs; runs beside -m or alone)\n"
+          "      --siti                 also compute ITU-T P.910 spatial / temporal information (si, ti) of the REFERENCE stream; the sequence values are\n"
+          "                             the maxima (YUV inputs; runs beside -m or alone)\n"
+          "      --siti-gain <X>        scale si and ti by X (with --siti) [default: 1]\n"
+          "      --siti-range <RANGE>   full: code values as they are; limited: gain 255/219, the limited-to-full-range stretch (with --siti)\n"
+          "                             [default: full] [possible values: full, limited]\n"
           "      --scenes               also find the scene cuts of the REFERENCE stream from luma histograms: per-frame scene_score and scene_cut,\n"
           "                             and scene_starts, the frames at which a scene begins (YUV inputs; runs beside -m or alone)\n"
           "      --scene-threshold <X>  a frame whose scene_score reaches X starts a scene, 0 < X <= 1 (with --scenes) [default: 0.5]\n"
@@ -166,7 +171,7 @@ int main(int argc, char **argv)
     SourceHints hints;
     uint32_t batch = 0 /* 0: chosen from the picture size */, device = 0, devices = 1, ranks = 0 /* 0: not asked for */, in_flight_pairs = 2;
     uint32_t xpsnr_fps_num = 0, xpsnr_fps_den = 1; // --xpsnr-fps (0: not given)
-    bool pipeline = true, full_sums = false, in_flight_given = false, scene_values_given = false, cambi_values_given = false, flip_values_given = false;
+    bool pipeline = true, full_sums = false, in_flight_given = false, scene_values_given = false, cambi_values_given = false, flip_values_given = false, siti_gain_given = false, siti_range_given = false, siti_limited = false;
     bool psnr_yuv_values_given = false, ssim_yuv_values_given = false, ciede_values_given = false;
     enum class Loop { Batched, Reference, Deferred } loop = Loop::Batched;
     std::vector<std::pair<int, long long>> tune;
@@ -248,6 +253,24 @@ int main(int argc, char **argv)
         else if (a == "--full-sums") full_sums = true;
         else if (a == "--motion") metrics.motion = true;
         else if (a == "--scenes") metrics.scenes = true;
+        else if (a == "--siti") metrics.siti = true;
+        else if (a == "--siti-gain") {
+            std::string v;
+            if (!value(v)) return bad("a value is required for '--siti-gain <X>' but none was supplied");
+            char *end = nullptr;
+            const double x = strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(x > 0.0) || !(x <= 1e6)) return bad("invalid value '" + v + "' for '--siti-gain <X>'\n  [0 < X <= 1e6]");
+            metrics.siti_gain = x;
+            siti_gain_given = true;
+        }
+        else if (a == "--siti-range") {
+            std::string v;
+            if (!value(v)) return bad("a value is required for '--siti-range <RANGE>' but none was supplied");
+            if (v == "limited") siti_limited = true;
+            else if (v == "full") siti_limited = false;
+            else return bad("invalid value '" + v + "' for '--siti-range <RANGE>'\n  [possible values: full, limited]");
+            siti_range_given = true;
+        }
         else if (a == "--scene-threshold") {
             std::string v;
             if (!value(v)) return bad("a value is required for '--scene-threshold <X>' but none was supplied");
@@ -332,6 +355,9 @@ int main(int argc, char **argv)
     }
     if (pos.size() != 2) return bad("the following required arguments were not provided:\n  <REFERENCE>\n  <DISTORTED>");
     if (scene_values_given && !metrics.scenes) return bad("'--scene-threshold <X>' and '--scene-bins <N>' belong to '--scenes'");
+    if ((siti_gain_given || siti_range_given) && !metrics.siti) return bad("'--siti-gain <X>' and '--siti-range <RANGE>' belong to '--siti'");
+    if (siti_gain_given && siti_range_given) return bad("'--siti-gain <X>' and '--siti-range <RANGE>' cannot be used together");
+    if (siti_limited) metrics.siti_gain = 255.0 / 219.0;
     if (cambi_values_given && !metrics.cambi) return bad("'--cambi-window <N>', '--cambi-topk <X>' and '--cambi-ref' belong to '-m cambi'");
     if (flip_values_given && !metrics.flip) return bad("'--flip-ppd <X>' and '--flip-map <PREFIX>' belong to '-m flip'");
     if (psnr_yuv_values_given && !metrics.psnr_yuv) return bad("'--psnr-yuv-cap' belongs to '-m psnr-yuv'");
@@ -380,6 +406,14 @@ int main(int argc, char **argv)
     if (metrics.adm) { // ADM, like VIF, runs on one device in the batched loop
         const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
         if (why) { log_line(L_ERROR, kTarget, std::string("-m adm does not run with ") + why); return EXIT_FAILURE; }
+    }
+
+    if (metrics.siti) { // TI compares consecutive pictures of ONE sequence on one device
+        const char *why = opts.every > 1 ? "--every > 1 (skipped pictures would never reach its history)"
+                        : devices != 1 ? "--devices (shards would cut its history)"
+                        : ranks > 0 ? "--ranks (shards would cut its history)"
+                        : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
+        if (why) { log_line(L_ERROR, kTarget, std::string("--siti does not run with ") + why); return EXIT_FAILURE; }
     }
 
     if (metrics.motion) { // motion compares consecutive pictures of ONE sequence on one device
@@ -635,7 +669,7 @@ int main(int argc, char **argv)
 
     std::unique_ptr<TurboMetrics> turbo;
     try {
-        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi && !metrics.flip && !metrics.psnr_yuv && !metrics.ssim_yuv && !metrics.psnr_hvs && !metrics.psnr_hvs_m && !metrics.ciede) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
+        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi && !metrics.flip && !metrics.psnr_yuv && !metrics.ssim_yuv && !metrics.psnr_hvs && !metrics.psnr_hvs_m && !metrics.ciede && !metrics.siti) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
         // a source that knows its length never needs more slots than it has pairs (a single image pair: one slot, one engine)
         const size_t known = std::min(source_ref->frame_count(), source_dis->frame_count());
         if (batch == 0) batch = auto_batch(source_ref->width(), source_ref->height());

@@ -4,6 +4,7 @@
 #include "../../include/turbo_metrics_xpsnr.h"
 #include "../../include/turbo_metrics_motion.h"
 #include "../../include/turbo_metrics_scene.h"
+#include "../../include/turbo_metrics_siti.h"
 #include "../../include/turbo_metrics_cambi.h"
 #include "../../include/turbo_metrics_flip.h"
 #include "../../include/turbo_metrics_yuv.h"
@@ -359,6 +360,90 @@ struct MotionRun {
     {
         if (ready.empty()) throw std::logic_error("motion: a picture's result is missing");
         const double v = ready.front();
+        ready.pop_front();
+        return v;
+    }
+};
+
+// ---- SI / TI ---------------------------------------------------------------------------------------------------------
+// libturbometrics_siti.so, loaded at run time like the motion library (a CLI run without --siti never loads it).  The REFERENCE luma of
+// every kept pair is handed over as a TM_MEM_HOST copy and computed batch by batch in stream order; the library keeps the previous
+// picture.  SI and TI at the chosen gain are the library's host functions of the exact sums: nothing here restates the definition.
+struct SitiRun {
+    struct Value { double si, ti; bool ti_valid; };
+    void *lib = nullptr;
+    int (*create)(tm_siti **, uint32_t, uint32_t, int, uint32_t, uint32_t) = nullptr;
+    void (*destroy)(tm_siti *) = nullptr;
+    int (*set_frame)(tm_siti *, uint32_t, const void *, size_t, int) = nullptr;
+    int (*compute_async)(tm_siti *, uint32_t) = nullptr;
+    int (*sync)(tm_siti *) = nullptr;
+    int (*get)(tm_siti *, uint32_t, uint32_t, tm_siti_frame *) = nullptr;
+    double (*si_of)(uint64_t, uint64_t, uint64_t, double) = nullptr;
+    double (*ti_of)(int64_t, uint64_t, uint64_t, uint32_t, double) = nullptr;
+    tm_siti *m = nullptr;
+    uint32_t w, h, batch;
+    double gain;
+    int layout = -1;
+    uint32_t bits = 8, filled = 0;
+    std::deque<Value> ready;
+
+    SitiRun(uint32_t w_, uint32_t h_, uint32_t batch_, double gain_) : w(w_), h(h_), batch(batch_), gain(gain_)
+    {
+        const char *path = getenv("TM_SITI_LIB");
+        lib = dlopen(path ? path : "libturbometrics_siti.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("--siti needs libturbometrics_siti.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_siti_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_siti_destroy");
+        set_frame = (decltype(set_frame))dlsym(lib, "tm_siti_set_frame");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_siti_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_siti_sync");
+        get = (decltype(get))dlsym(lib, "tm_siti_get");
+        si_of = (decltype(si_of))dlsym(lib, "tm_siti_si");
+        ti_of = (decltype(ti_of))dlsym(lib, "tm_siti_ti");
+        if (!create || !destroy || !set_frame || !compute_async || !sync || !get || !si_of || !ti_of)
+            throw std::runtime_error("libturbometrics_siti.so does not export include/turbo_metrics_siti.h");
+    }
+    ~SitiRun()
+    {
+        if (m) destroy(m);
+        if (lib) dlclose(lib);
+    }
+    void push(const HwFrame &r)
+    {
+        int l;
+        uint32_t b;
+        switch (r.kind) {
+        case HwFrame::NvDecNV12: l = TM_SITI_Y8; b = 8; break;
+        case HwFrame::NvDecP016: l = TM_SITI_Y16_MSB; b = 10; break;
+        case HwFrame::Planar420: b = (uint32_t)r.bits; l = b == 8 ? TM_SITI_Y8 : TM_SITI_Y16_LOW; break;
+        case HwFrame::Planar420P10: l = TM_SITI_Y10_PACKED; b = 10; break;
+        default: throw std::runtime_error("siti needs YUV input (Y4M, raw planar YUV or decoded video), not RGB images");
+        }
+        if (!m) {
+            layout = l; bits = b;
+            chk(create(&m, w, h, layout, bits, batch), "tm_siti_create");
+        } else if (l != layout || b != bits) {
+            throw std::runtime_error("siti: the YUV layout changed inside the stream");
+        }
+        chk(set_frame(m, filled, r.data, r.pitch, r.device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_siti_set_frame");
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(m, filled), "tm_siti_compute_async");
+        chk(sync(m), "tm_siti_sync");
+        std::vector<tm_siti_frame> out(filled);
+        chk(get(m, 0, filled, out.data()), "tm_siti_get");
+        const uint64_t n = (uint64_t)w * h, n_si = (uint64_t)(w - 2) * (h - 2);
+        for (const tm_siti_frame &f : out)
+            ready.push_back({si_of(f.s1, f.s2, n_si, gain), f.ti_valid ? ti_of(f.t1, f.t2, n, bits, gain) : 0.0, f.ti_valid != 0});
+        filled = 0;
+    }
+    Value pop()
+    {
+        if (ready.empty()) throw std::logic_error("siti: a picture's result is missing");
+        const Value v = ready.front();
         ready.pop_front();
         return v;
     }
@@ -1200,6 +1285,7 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
 {
     if (metrics_.xpsnr) xp_ = std::make_unique<XpsnrRun>(w_, h_, batch_);
     if (metrics_.motion) mo_ = std::make_unique<MotionRun>(w_, h_, batch_);
+    if (metrics_.siti) si_ = std::make_unique<SitiRun>(w_, h_, batch_, metrics_.siti_gain);
     if (metrics_.vif) vf_ = std::make_unique<VifRun>(w_, h_, batch_);
     if (metrics_.adm) ad_ = std::make_unique<AdmRun>(w_, h_, batch_);
     if (metrics_.scenes) sc_ = std::make_unique<SceneRun>(w_, h_, batch_, metrics_.scene_bins, metrics_.scene_threshold);
@@ -1209,7 +1295,7 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
     if (metrics_.psnr_yuv || metrics_.ssim_yuv) yv_ = std::make_unique<YuvRun>(w_, h_, batch_, metrics_.psnr_yuv_cap, metrics_.ssim_yuv_map);
     if (metrics_.psnr_hvs || metrics_.psnr_hvs_m) hv_ = std::make_unique<HvsRun>(w_, h_, batch_);
     if (metrics_.ciede) ci_ = std::make_unique<CiedeRun>(w_, h_, batch_, metrics_.ciede_libvmaf, metrics_.ciede_map);
-    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_ || hv_ || ci_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
+    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_ || hv_ || ci_ || si_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -1513,6 +1599,9 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     if (metrics_.psnr_hvs_m) s_hv[1].emplace();
     std::optional<std::vector<double>> s_ci[2]; // kCiedeNames
     if (metrics_.ciede) { s_ci[0].emplace(); s_ci[1].emplace(); }
+    std::optional<std::vector<double>> s_si, s_ti; // --siti: every frame's si and ti (the first picture's ti: 0)
+    std::vector<double> ti_valid;                  // ... and the ti values its statistics are of: the first picture has none
+    if (si_) { s_si.emplace(); s_ti.emplace(); }
     std::optional<FrameScores> held;
     auto emit = [&](const FrameScores &r) {
         if (on_frame) on_frame(r);
@@ -1524,6 +1613,11 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (s_sc) {
             s_sc->push_back(*r.scene_score);
             if (compute_count == 0 || *r.scene_cut) scene_starts.push_back(compute_count);
+        }
+        if (s_si) {
+            s_si->push_back(*r.si);
+            s_ti->push_back(*r.ti);
+            if (r.ti_valid) ti_valid.push_back(*r.ti);
         }
         ++compute_count;
     };
@@ -1585,6 +1679,10 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
                 const std::array<double, 2> v = ci_->pop();
                 for (int k = 0; k < 2; ++k) { r.ciede[k] = v[k]; s_ci[k]->push_back(v[k]); }
             }
+            if (si_) {
+                const SitiRun::Value v = si_->pop();
+                r.si = v.si; r.ti = v.ti; r.ti_valid = v.ti_valid;
+            }
             if (mo_) {
                 r.motion = mo_->pop();
                 if (held) {
@@ -1613,6 +1711,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (yv_) yv_->flush();
         if (hv_) hv_->flush();
         if (ci_) ci_->flush();
+        if (si_) si_->flush();
         in_flight[i] = true;
     };
 
@@ -1690,6 +1789,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (yv_) yv_->push(fref, fdis);
         if (hv_) hv_->push(fref, fdis);
         if (ci_) ci_->push(fref, fdis, cref, cdis);
+        if (si_) si_->push(fref);
         if (eng_[cur]) {
             set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
             set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
@@ -1728,7 +1828,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_ || hv_ || ci_))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_ || hv_ || ci_ || si_))
         throw NoFramesSelected();
     if (xp_) {
         std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
@@ -1736,6 +1836,14 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
             *dst[c] = MetricAggregate::from(std::move(*s_xp[c]));
             (*dst[c])->sequence = xp_->sequence_score(c);
         }
+    }
+    if (s_si) { // the sequence values are the maxima (P.910); a stream of one picture has no TI: its sequence TI is 0
+        res.si = MetricAggregate::from(std::move(*s_si));
+        res.si->sequence = res.si->stats.max;
+        res.ti.emplace(); // scores: one per frame like every other metric; stats: of the frames that have a TI (none: all zero)
+        res.ti->stats = ti_valid.empty() ? Stats{} : Stats::compute(ti_valid);
+        res.ti->scores = std::move(*s_ti);
+        res.ti->sequence = res.ti->stats.max;
     }
     if (s_mo) {
         res.motion = MetricAggregate::from(std::move(*s_mo));

@@ -63,6 +63,10 @@ struct Metrics {
     // the factors libvmaf is recalled to use) and --ciede-map (a prefix: every pair's dE00 map as PREFIX%06d.pfm); not an engine metric
     bool ciede = false, ciede_libvmaf = false;
     std::string ciede_map;
+    // ITU-T P.910 spatial / temporal information of the REFERENCE stream (include/turbo_metrics_siti.h, libturbometrics_siti.so): the CLI's
+    // --siti, --siti-gain (1: code values as they are) and --siti-range limited (gain 255 / 219); not an engine metric
+    bool siti = false;
+    double siti_gain = 1.0;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -110,6 +114,8 @@ struct MetricsResults {
     std::optional<MetricAggregate> hvs[2];
     // -m ciede2000: [0] ciede2000 (the score), [1] ciede2000_de (the mean dE00); sequence: from the summed dE00 over the summed positions; names: kCiedeNames
     std::optional<MetricAggregate> ciede[2];
+    // --siti: si and ti of every frame; the first frame has no TI: its score is 0 and ti's stats leave it out; sequence: the maximum (P.910)
+    std::optional<MetricAggregate> si, ti;
 };
 
 struct MetricsStats {
@@ -140,6 +146,8 @@ struct FrameScores {
     std::optional<double> yuv[8]; // kYuvNames
     std::optional<double> hvs[2]; // kHvsNames
     std::optional<double> ciede[2]; // kCiedeNames
+    std::optional<double> si, ti;   // --siti; ti_valid false: the first picture of the stream, ti is 0 and stays out of the aggregates
+    bool ti_valid = false;
 };
 
 extern const char *const kYuvNames[8];
@@ -341,6 +349,7 @@ private:
     std::unique_ptr<struct HvsRun> hv_;                       // metrics_.psnr_hvs / psnr_hvs_m: the PSNR-HVS library's state (likewise; no history)
     std::unique_ptr<struct FlipRun> fl_;                      // metrics_.flip: the FLIP library's state (likewise; no history)
     std::unique_ptr<struct SceneRun> sc_;                     // metrics_.scenes: the reference stream's previous histogram (likewise)
+    std::unique_ptr<struct SitiRun> si_;                      // metrics_.siti: the reference stream's SI / TI state (likewise)
     std::unique_ptr<struct MotionRun> mo_;                    // metrics_.motion: the reference stream's motion state (likewise)
     bool full_sums_ = false;                                  // settings replayed on an engine that is created later
     std::vector<std::pair<int, long long>> debug_params_;
