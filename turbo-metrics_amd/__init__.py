@@ -15,6 +15,7 @@ C ABI) with a host-side mirror of the reference's operator interface.
   hvs     -- ctypes binding of include/turbo_metrics_hvs.h (libturbometrics_hvs.so): Hvs, PSNR-HVS and PSNR-HVS-M of the lumas of frame pairs
   ciede   -- ctypes binding of include/turbo_metrics_ciede.h (libturbometrics_ciede.so): Ciede, CIEDE2000 of 4:2:0 frame pairs
   siti    -- ctypes binding of include/turbo_metrics_siti.h (libturbometrics_siti.so): Siti, ITU-T P.910 spatial / temporal information of one stream
+  gmsd    -- ctypes binding of include/turbo_metrics_gmsd.h (libturbometrics_gmsd.so): Gmsd, the gradient magnitude similarity deviation of the lumas of frame pairs
 
 There is no CPU implementation in this package: without the HIP library (or without a gfx950 GPU)
 the operators raise.
@@ -42,3 +43,5 @@ from . import ciede  # noqa: F401,E402
 from .ciede import Ciede, CiedeFrame  # noqa: F401,E402
 from . import siti  # noqa: F401,E402
 from .siti import Siti, SitiFrame  # noqa: F401,E402
+from . import gmsd  # noqa: F401,E402
+from .gmsd import Gmsd, GmsdFrame  # noqa: F401,E402

@@ -50,6 +50,7 @@ void usage(std::ostream &os)
           "                             [further values, each described below: vif, adm, cambi, flip, psnr-yuv, ssim-yuv]\n"
           "                             [and: psnr-hvs, psnr-hvs-m]\n"
           "                             [and: ciede2000]\n"
+          "                             [and: gmsd]\n"
           "                             and vif: VMAF's VIF of the luma planes, four scales (YUV inputs; runs beside the others or alone)\n"
           "                             and adm: VMAF's ADM of the luma planes, adm2 and four scales (likewise)\n"
           "      --every <EVERY>        Only compute metrics every few frames [default: 0]\n"
@@ -101,6 +102,12 @@ void usage(std::ostream &os)
           "                             values come from the summed dE00; alone or beside the other -m values\n"
           "      --ciede-libvmaf        the matrix and the factors kL, kC, kH = 0.65, 1, 4 libvmaf's ciede feature is recalled to use (with -m ciede2000)\n"
           "      --ciede-map <PREFIX>   write every pair's dE00 map as a one-channel PFM, PREFIX000000.pfm, PREFIX000001.pfm, ... (with -m ciede2000)\n"
+          "  -m gmsd                    GMSD, the gradient magnitude similarity deviation (Xue et al. 2014) of the luma planes of YUV pairs: the standard\n"
+          "                             deviation of the similarity of the Prewitt gradient magnitudes after a 2x2 mean and 2:1 decimation (0: identical),\n"
+          "                             and gmsm, its mean: gmsd, gmsm, after all other columns; the sequence values are pooled over all positions of all\n"
+          "                             pairs; alone or beside the other -m values\n"
+          "      --gmsd-population      divide by N instead of N - 1 in the standard deviation (with -m gmsd)\n"
+          "      --gmsd-map <PREFIX>    write every pair's GMS map as a one-channel PFM, PREFIX000000.pfm, PREFIX000001.pfm, ... (with -m gmsd)\n"
           "      --psnr-yuv-cap         cap every PSNR at libvmaf's 6 * depth + 12 dB instead of printing inf (with -m psnr-yuv)\n"
           "      --ssim-yuv-map <PREFIX>  write every pair's luma SSIM window map as a one-channel PFM, PREFIX000000.pfm, ... (with -m ssim-yuv)\n"
           "      --cambi-window <N>     side of the window the banding is looked for in, 3 ... 127 (with -m cambi) [default: 63 * width / 3840, at least 3]\n"
@@ -172,7 +179,7 @@ int main(int argc, char **argv)
     uint32_t batch = 0 /* 0: chosen from the picture size */, device = 0, devices = 1, ranks = 0 /* 0: not asked for */, in_flight_pairs = 2;
     uint32_t xpsnr_fps_num = 0, xpsnr_fps_den = 1; // --xpsnr-fps (0: not given)
     bool pipeline = true, full_sums = false, in_flight_given = false, scene_values_given = false, cambi_values_given = false, flip_values_given = false, siti_gain_given = false, siti_range_given = false, siti_limited = false;
-    bool psnr_yuv_values_given = false, ssim_yuv_values_given = false, ciede_values_given = false;
+    bool psnr_yuv_values_given = false, ssim_yuv_values_given = false, ciede_values_given = false, gmsd_values_given = false;
     enum class Loop { Batched, Reference, Deferred } loop = Loop::Batched;
     std::vector<std::pair<int, long long>> tune;
 
@@ -214,7 +221,8 @@ int main(int argc, char **argv)
             else if (s == "psnr-hvs") metrics.psnr_hvs = true;
             else if (s == "psnr-hvs-m") metrics.psnr_hvs_m = true;
             else if (s == "ciede2000") metrics.ciede = true;
-            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv, psnr-hvs, psnr-hvs-m] [and: ciede2000]");
+            else if (s == "gmsd") metrics.gmsd = true;
+            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv, psnr-hvs, psnr-hvs-m] [and: ciede2000] [and: gmsd]");
         } else if (a.rfind("-m", 0) == 0 && a.size() > 2 && a[1] == 'm') { // -mpsnr
             const std::string s = a.substr(2);
             if (s == "psnr") metrics.psnr = true; else if (s == "ssim") metrics.ssim = true; else if (s == "msssim") metrics.msssim = true;
@@ -229,7 +237,8 @@ int main(int argc, char **argv)
             else if (s == "psnr-hvs") metrics.psnr_hvs = true;
             else if (s == "psnr-hvs-m") metrics.psnr_hvs_m = true;
             else if (s == "ciede2000") metrics.ciede = true;
-            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv, psnr-hvs, psnr-hvs-m] [and: ciede2000]");
+            else if (s == "gmsd") metrics.gmsd = true;
+            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv, psnr-hvs, psnr-hvs-m] [and: ciede2000] [and: gmsd]");
         } else if (a == "--every") { if (!u32(opts.every)) return bad("invalid value for '--every <EVERY>'"); }
         else if (a == "--skip") { if (!u32(opts.skip)) return bad("invalid value for '--skip <SKIP>'"); }
         else if (a == "--skip-ref") { if (!u32(opts.skip_ref)) return bad("invalid value for '--skip-ref <SKIP_REF>'"); }
@@ -329,6 +338,11 @@ int main(int argc, char **argv)
             if (!value(metrics.ciede_map) || metrics.ciede_map.empty()) return bad("a value is required for '--ciede-map <PREFIX>' but none was supplied");
             ciede_values_given = true;
         }
+        else if (a == "--gmsd-population") { metrics.gmsd_population = true; gmsd_values_given = true; }
+        else if (a == "--gmsd-map") {
+            if (!value(metrics.gmsd_map) || metrics.gmsd_map.empty()) return bad("a value is required for '--gmsd-map <PREFIX>' but none was supplied");
+            gmsd_values_given = true;
+        }
         else if (a == "--cambi-ref") { metrics.cambi_ref = true; cambi_values_given = true; }
         else if (a == "--xpsnr-fps") {
             std::string v;
@@ -370,6 +384,11 @@ int main(int argc, char **argv)
     if (metrics.ciede) { // like -m psnr-yuv: one device, the batched loop
         const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
         if (why) { log_line(L_ERROR, kTarget, std::string("-m ciede2000 does not run with ") + why); return EXIT_FAILURE; }
+    }
+    if (gmsd_values_given && !metrics.gmsd) return bad("'--gmsd-population' and '--gmsd-map <PREFIX>' belong to '-m gmsd'");
+    if (metrics.gmsd) { // like -m psnr-hvs: one device, the batched loop
+        const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
+        if (why) { log_line(L_ERROR, kTarget, std::string("-m gmsd does not run with ") + why); return EXIT_FAILURE; }
     }
     if (metrics.psnr_hvs || metrics.psnr_hvs_m) { // like VIF: one device, the batched loop
         const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
@@ -669,7 +688,7 @@ int main(int argc, char **argv)
 
     std::unique_ptr<TurboMetrics> turbo;
     try {
-        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi && !metrics.flip && !metrics.psnr_yuv && !metrics.ssim_yuv && !metrics.psnr_hvs && !metrics.psnr_hvs_m && !metrics.ciede && !metrics.siti) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
+        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi && !metrics.flip && !metrics.psnr_yuv && !metrics.ssim_yuv && !metrics.psnr_hvs && !metrics.psnr_hvs_m && !metrics.ciede && !metrics.siti && !metrics.gmsd) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
         // a source that knows its length never needs more slots than it has pairs (a single image pair: one slot, one engine)
         const size_t known = std::min(source_ref->frame_count(), source_dis->frame_count());
         if (batch == 0) batch = auto_batch(source_ref->width(), source_ref->height());

@@ -9,6 +9,7 @@
 #include "../../include/turbo_metrics_flip.h"
 #include "../../include/turbo_metrics_yuv.h"
 #include "../../include/turbo_metrics_hvs.h"
+#include "../../include/turbo_metrics_gmsd.h"
 #include "../../include/turbo_metrics_ciede.h"
 #include "frame_sources.hpp" // write_pfm_gray
 #include "../../include/turbo_metrics_vif.h"
@@ -961,6 +962,123 @@ struct HvsRun {
     double sequence_score(int k) const { return psnr(sum_s[k], sum_blocks, bits); }
 };
 
+// ---- GMSD ----------------------------------------------------------------------------------------------------------------
+// libturbometrics_gmsd.so, loaded at run time like the PSNR-HVS library (a CLI run without -m gmsd never loads it).  The lumas of every kept
+// pair are handed over as -m psnr-hvs hands them over and computed batch by batch in stream order; a pair's two values (kGmsdNames: gmsd and
+// gmsm, the mean GMS) wait in `ready` until the engine's scores of the same pair are drained.  The sequence values: the library's host
+// functions of the summed E1, E2 and N -- pooled over all positions of all pairs.  --gmsd-map: every pair's GMS map goes to PREFIX%06d.pfm,
+// numbered in the order the pairs are computed.  No history: --every is fine.
+const char *const kGmsdNames[2] = {"gmsd", "gmsm"};
+
+struct GmsdRun {
+    void *lib = nullptr;
+    int (*create)(tm_gmsd **, uint32_t, uint32_t, int, uint32_t, uint32_t, uint32_t) = nullptr;
+    void (*destroy)(tm_gmsd *) = nullptr;
+    int (*set_pair)(tm_gmsd *, uint32_t, const void *, const void *, size_t, size_t, int) = nullptr;
+    int (*compute_async)(tm_gmsd *, uint32_t) = nullptr;
+    int (*sync)(tm_gmsd *) = nullptr;
+    int (*get)(tm_gmsd *, uint32_t, uint32_t, tm_gmsd_frame *) = nullptr;
+    int (*get_map)(tm_gmsd *, uint32_t, float *, size_t) = nullptr;
+    double (*score)(double, double, uint64_t, int) = nullptr;
+    double (*mean)(double, uint64_t) = nullptr;
+    tm_gmsd *v = nullptr;
+    uint32_t w, h, batch;
+    bool population;
+    std::string map_prefix;
+    int layout = -1;
+    uint32_t bits = 8, filled = 0;
+    size_t written = 0;
+    std::vector<float> map;
+    std::deque<std::array<double, 2>> ready;
+    double sum_e1 = 0.0, sum_e2 = 0.0;
+    uint64_t sum_n = 0;
+
+    GmsdRun(uint32_t w_, uint32_t h_, uint32_t batch_, bool population_, std::string prefix)
+        : w(w_), h(h_), batch(batch_), population(population_), map_prefix(std::move(prefix))
+    {
+        const char *path = getenv("TM_GMSD_LIB");
+        lib = dlopen(path ? path : "libturbometrics_gmsd.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("-m gmsd needs libturbometrics_gmsd.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_gmsd_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_gmsd_destroy");
+        set_pair = (decltype(set_pair))dlsym(lib, "tm_gmsd_set_pair");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_gmsd_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_gmsd_sync");
+        get = (decltype(get))dlsym(lib, "tm_gmsd_get");
+        get_map = (decltype(get_map))dlsym(lib, "tm_gmsd_map");
+        score = (decltype(score))dlsym(lib, "tm_gmsd_score");
+        mean = (decltype(mean))dlsym(lib, "tm_gmsd_mean");
+        if (!create || !destroy || !set_pair || !compute_async || !sync || !get || !get_map || !score || !mean) {
+            dlclose(lib); // the destructor does not run for an object whose constructor throws
+            throw std::runtime_error("libturbometrics_gmsd.so does not export include/turbo_metrics_gmsd.h");
+        }
+    }
+    ~GmsdRun()
+    {
+        if (v) destroy(v);
+        if (lib) dlclose(lib);
+    }
+    static void layout_of(const HwFrame &f, int &l, uint32_t &b)
+    {
+        switch (f.kind) {
+        case HwFrame::NvDecNV12: l = TM_GMSD_Y8; b = 8; return;
+        case HwFrame::NvDecP016: l = TM_GMSD_Y16_MSB; b = 10; return;
+        case HwFrame::Planar420: b = (uint32_t)f.bits; l = b == 8 ? TM_GMSD_Y8 : TM_GMSD_Y16_LOW; return;
+        case HwFrame::Planar420P10: l = TM_GMSD_Y10_PACKED; b = 10; return;
+        default: throw std::runtime_error("gmsd needs YUV input (Y4M, raw planar YUV or decoded video), not RGB images");
+        }
+    }
+    void push(const HwFrame &r, const HwFrame &d)
+    {
+        int lr, ld;
+        uint32_t br, bd;
+        layout_of(r, lr, br);
+        layout_of(d, ld, bd);
+        if (lr != ld || br != bd || r.device != d.device) throw std::runtime_error("gmsd needs reference and distorted in the same YUV layout and bit depth");
+        if (!v) {
+            layout = lr; bits = br;
+            const int rc = create(&v, w, h, layout, bits, batch, map_prefix.empty() ? 0u : (uint32_t)TM_GMSD_MAPS);
+            if (rc == TM_ERR_UNSUPPORTED) throw std::runtime_error("gmsd takes pictures of 4 x 4 to 32768 x 32768 samples");
+            chk(rc, "tm_gmsd_create");
+        } else if (lr != layout || br != bits) {
+            throw std::runtime_error("gmsd: the YUV layout changed inside the stream");
+        }
+        chk(set_pair(v, filled, r.data, d.data, r.pitch, d.pitch, r.device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_gmsd_set_pair");
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(v, filled), "tm_gmsd_compute_async");
+        chk(sync(v), "tm_gmsd_sync");
+        std::vector<tm_gmsd_frame> out(filled);
+        chk(get(v, 0, filled, out.data()), "tm_gmsd_get");
+        const uint32_t w2 = (w + 1) / 2, h2 = (h + 1) / 2;
+        for (uint32_t i = 0; i < filled; ++i) {
+            const tm_gmsd_frame &f = out[i];
+            ready.push_back({score(f.e1, f.e2, f.n, population), mean(f.e1, f.n)});
+            sum_e1 += f.e1; sum_e2 += f.e2;
+            sum_n += f.n;
+            if (map_prefix.empty()) continue;
+            map.resize((size_t)w2 * h2);
+            chk(get_map(v, i, map.data(), (size_t)w2 * sizeof(float)), "tm_gmsd_map");
+            char num[32];
+            snprintf(num, sizeof num, "%06zu.pfm", written++);
+            write_pfm_gray(map_prefix + num, w2, h2, map.data());
+        }
+        filled = 0;
+    }
+    std::array<double, 2> pop()
+    {
+        if (ready.empty()) throw std::logic_error("gmsd: a pair's result is missing");
+        const std::array<double, 2> s = ready.front();
+        ready.pop_front();
+        return s;
+    }
+    // the sequence value of column k (kGmsdNames)
+    double sequence_score(int k) const { return k ? mean(sum_e1, sum_n) : score(sum_e1, sum_e2, sum_n, population); }
+};
+
 // ---- CIEDE2000 ---------------------------------------------------------------------------------------------------------
 // libturbometrics_ciede.so, loaded at run time like the YUV library (a CLI run without -m ciede2000 never loads it).  Pairs are handed over
 // as -m psnr-yuv hands them over and computed batch by batch in stream order; a pair's two values (kCiedeNames: the score and the mean dE00)
@@ -1295,7 +1413,8 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
     if (metrics_.psnr_yuv || metrics_.ssim_yuv) yv_ = std::make_unique<YuvRun>(w_, h_, batch_, metrics_.psnr_yuv_cap, metrics_.ssim_yuv_map);
     if (metrics_.psnr_hvs || metrics_.psnr_hvs_m) hv_ = std::make_unique<HvsRun>(w_, h_, batch_);
     if (metrics_.ciede) ci_ = std::make_unique<CiedeRun>(w_, h_, batch_, metrics_.ciede_libvmaf, metrics_.ciede_map);
-    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_ || hv_ || ci_ || si_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
+    if (metrics_.gmsd) gm_ = std::make_unique<GmsdRun>(w_, h_, batch_, metrics_.gmsd_population, metrics_.gmsd_map);
+    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_ || hv_ || ci_ || si_ || gm_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -1602,6 +1721,8 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     std::optional<std::vector<double>> s_si, s_ti; // --siti: every frame's si and ti (the first picture's ti: 0)
     std::vector<double> ti_valid;                  // ... and the ti values its statistics are of: the first picture has none
     if (si_) { s_si.emplace(); s_ti.emplace(); }
+    std::optional<std::vector<double>> s_gm[2]; // kGmsdNames
+    if (gm_) { s_gm[0].emplace(); s_gm[1].emplace(); }
     std::optional<FrameScores> held;
     auto emit = [&](const FrameScores &r) {
         if (on_frame) on_frame(r);
@@ -1683,6 +1804,10 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
                 const SitiRun::Value v = si_->pop();
                 r.si = v.si; r.ti = v.ti; r.ti_valid = v.ti_valid;
             }
+            if (gm_) {
+                const std::array<double, 2> v = gm_->pop();
+                for (int k = 0; k < 2; ++k) { r.gmsd[k] = v[k]; s_gm[k]->push_back(v[k]); }
+            }
             if (mo_) {
                 r.motion = mo_->pop();
                 if (held) {
@@ -1712,6 +1837,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (hv_) hv_->flush();
         if (ci_) ci_->flush();
         if (si_) si_->flush();
+        if (gm_) gm_->flush();
         in_flight[i] = true;
     };
 
@@ -1790,6 +1916,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (hv_) hv_->push(fref, fdis);
         if (ci_) ci_->push(fref, fdis, cref, cdis);
         if (si_) si_->push(fref);
+        if (gm_) gm_->push(fref, fdis);
         if (eng_[cur]) {
             set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
             set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
@@ -1828,7 +1955,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_ || hv_ || ci_ || si_))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_ || hv_ || ci_ || si_ || gm_))
         throw NoFramesSelected();
     if (xp_) {
         std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
@@ -1888,6 +2015,11 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (s_ci[k]) {
             res.ciede[k] = MetricAggregate::from(std::move(*s_ci[k]));
             res.ciede[k]->sequence = ci_->sequence_score(k);
+        }
+    for (int k = 0; k < 2; ++k)
+        if (s_gm[k]) {
+            res.gmsd[k] = MetricAggregate::from(std::move(*s_gm[k]));
+            res.gmsd[k]->sequence = gm_->sequence_score(k);
         }
     if (s_psnr) res.psnr = MetricAggregate::from(std::move(*s_psnr));
     if (s_ssim) res.ssim = MetricAggregate::from(std::move(*s_ssim));

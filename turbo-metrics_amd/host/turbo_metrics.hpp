@@ -67,6 +67,11 @@ struct Metrics {
     // --siti, --siti-gain (1: code values as they are) and --siti-range limited (gain 255 / 219); not an engine metric
     bool siti = false;
     double siti_gain = 1.0;
+    // GMSD, the gradient magnitude similarity deviation of the luma planes (include/turbo_metrics_gmsd.h, libturbometrics_gmsd.so): the CLI's
+    // -m gmsd, --gmsd-population (the standard deviation divides by N, not N - 1) and --gmsd-map (a prefix: every pair's GMS map as
+    // PREFIX%06d.pfm); not an engine metric
+    bool gmsd = false, gmsd_population = false;
+    std::string gmsd_map;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -116,6 +121,8 @@ struct MetricsResults {
     std::optional<MetricAggregate> ciede[2];
     // --siti: si and ti of every frame; the first frame has no TI: its score is 0 and ti's stats leave it out; sequence: the maximum (P.910)
     std::optional<MetricAggregate> si, ti;
+    // -m gmsd: [0] gmsd, [1] gmsm (the mean GMS); sequence: from the summed E1, E2 and N, pooled over all positions of all pairs; names: kGmsdNames
+    std::optional<MetricAggregate> gmsd[2];
 };
 
 struct MetricsStats {
@@ -148,10 +155,12 @@ struct FrameScores {
     std::optional<double> ciede[2]; // kCiedeNames
     std::optional<double> si, ti;   // --siti; ti_valid false: the first picture of the stream, ti is 0 and stays out of the aggregates
     bool ti_valid = false;
+    std::optional<double> gmsd[2]; // kGmsdNames
 };
 
 extern const char *const kYuvNames[8];
 extern const char *const kHvsNames[2];
+extern const char *const kGmsdNames[2];
 extern const char *const kCiedeNames[2];
 
 // ---- colour metadata (H.273 code points the reference understands, codec-bitstream/src/lib.rs:98-248) ----------
@@ -346,6 +355,7 @@ private:
     std::unique_ptr<struct CambiRun> cb_, cbr_;               // metrics_.cambi / cambi_ref: the CAMBI library's state per stream (likewise; no history)
     std::unique_ptr<struct YuvRun> yv_;                       // metrics_.psnr_yuv / ssim_yuv: the YUV PSNR / SSIM library's state (likewise; no history)
     std::unique_ptr<struct CiedeRun> ci_;                     // metrics_.ciede: the CIEDE2000 library's state (likewise; no history)
+    std::unique_ptr<struct GmsdRun> gm_;                      // metrics_.gmsd: the GMSD library's state (likewise; no history)
     std::unique_ptr<struct HvsRun> hv_;                       // metrics_.psnr_hvs / psnr_hvs_m: the PSNR-HVS library's state (likewise; no history)
     std::unique_ptr<struct FlipRun> fl_;                      // metrics_.flip: the FLIP library's state (likewise; no history)
     std::unique_ptr<struct SceneRun> sc_;                     // metrics_.scenes: the reference stream's previous histogram (likewise)
