@@ -16,6 +16,7 @@ C ABI) with a host-side mirror of the reference's operator interface.
   ciede   -- ctypes binding of include/turbo_metrics_ciede.h (libturbometrics_ciede.so): Ciede, CIEDE2000 of 4:2:0 frame pairs
   siti    -- ctypes binding of include/turbo_metrics_siti.h (libturbometrics_siti.so): Siti, ITU-T P.910 spatial / temporal information of one stream
   gmsd    -- ctypes binding of include/turbo_metrics_gmsd.h (libturbometrics_gmsd.so): Gmsd, the gradient magnitude similarity deviation of the lumas of frame pairs
+  haarpsi -- ctypes binding of include/turbo_metrics_haarpsi.h (libturbometrics_haarpsi.so): HaarPsi, the Haar wavelet-based perceptual similarity index of the lumas of frame pairs
 
 There is no CPU implementation in this package: without the HIP library (or without a gfx950 GPU)
 the operators raise.
@@ -45,3 +46,5 @@ from . import siti  # noqa: F401,E402
 from .siti import Siti, SitiFrame  # noqa: F401,E402
 from . import gmsd  # noqa: F401,E402
 from .gmsd import Gmsd, GmsdFrame  # noqa: F401,E402
+from . import haarpsi  # noqa: F401,E402
+from .haarpsi import HaarPsi, HaarPsiFrame  # noqa: F401,E402

@@ -10,6 +10,7 @@
 #include "../../include/turbo_metrics_yuv.h"
 #include "../../include/turbo_metrics_hvs.h"
 #include "../../include/turbo_metrics_gmsd.h"
+#include "../../include/turbo_metrics_haarpsi.h"
 #include "../../include/turbo_metrics_ciede.h"
 #include "frame_sources.hpp" // write_pfm_gray
 #include "../../include/turbo_metrics_vif.h"
@@ -1079,6 +1080,116 @@ struct GmsdRun {
     double sequence_score(int k) const { return k ? mean(sum_e1, sum_n) : score(sum_e1, sum_e2, sum_n, population); }
 };
 
+// ---- HaarPSI -------------------------------------------------------------------------------------------------------------
+// libturbometrics_haarpsi.so, loaded at run time like the GMSD library (a CLI run without -m haarpsi never loads it).  The lumas of every
+// kept pair are handed over as -m gmsd hands them over and computed batch by batch in stream order; a pair's value waits in `ready` until
+// the engine's scores of the same pair are drained.  The sequence value: the library's host function of the summed Q and WS.
+// --haarpsi-map: every pair's local similarity map goes to PREFIX%06d.pfm, numbered in the order the pairs are computed.  No history:
+// --every is fine.
+struct HaarpsiRun {
+    void *lib = nullptr;
+    int (*create)(tm_haarpsi **, uint32_t, uint32_t, int, uint32_t, uint32_t, uint32_t) = nullptr;
+    void (*destroy)(tm_haarpsi *) = nullptr;
+    int (*set_pair)(tm_haarpsi *, uint32_t, const void *, const void *, size_t, size_t, int) = nullptr;
+    int (*compute_async)(tm_haarpsi *, uint32_t) = nullptr;
+    int (*sync)(tm_haarpsi *) = nullptr;
+    int (*get)(tm_haarpsi *, uint32_t, uint32_t, tm_haarpsi_frame *) = nullptr;
+    int (*get_map)(tm_haarpsi *, uint32_t, float *, size_t) = nullptr;
+    double (*score)(double, uint64_t) = nullptr;
+    tm_haarpsi *v = nullptr;
+    uint32_t w, h, batch;
+    std::string map_prefix;
+    int layout = -1;
+    uint32_t bits = 8, filled = 0;
+    size_t written = 0;
+    std::vector<float> map;
+    std::deque<double> ready;
+    double sum_q = 0.0;
+    uint64_t sum_ws = 0;
+
+    HaarpsiRun(uint32_t w_, uint32_t h_, uint32_t batch_, std::string prefix) : w(w_), h(h_), batch(batch_), map_prefix(std::move(prefix))
+    {
+        const char *path = getenv("TM_HAARPSI_LIB");
+        lib = dlopen(path ? path : "libturbometrics_haarpsi.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("-m haarpsi needs libturbometrics_haarpsi.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_haarpsi_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_haarpsi_destroy");
+        set_pair = (decltype(set_pair))dlsym(lib, "tm_haarpsi_set_pair");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_haarpsi_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_haarpsi_sync");
+        get = (decltype(get))dlsym(lib, "tm_haarpsi_get");
+        get_map = (decltype(get_map))dlsym(lib, "tm_haarpsi_map");
+        score = (decltype(score))dlsym(lib, "tm_haarpsi_score");
+        if (!create || !destroy || !set_pair || !compute_async || !sync || !get || !get_map || !score) {
+            dlclose(lib); // the destructor does not run for an object whose constructor throws
+            throw std::runtime_error("libturbometrics_haarpsi.so does not export include/turbo_metrics_haarpsi.h");
+        }
+    }
+    ~HaarpsiRun()
+    {
+        if (v) destroy(v);
+        if (lib) dlclose(lib);
+    }
+    static void layout_of(const HwFrame &f, int &l, uint32_t &b)
+    {
+        switch (f.kind) {
+        case HwFrame::NvDecNV12: l = TM_HAARPSI_Y8; b = 8; return;
+        case HwFrame::NvDecP016: l = TM_HAARPSI_Y16_MSB; b = 10; return;
+        case HwFrame::Planar420: b = (uint32_t)f.bits; l = b == 8 ? TM_HAARPSI_Y8 : TM_HAARPSI_Y16_LOW; return;
+        case HwFrame::Planar420P10: l = TM_HAARPSI_Y10_PACKED; b = 10; return;
+        default: throw std::runtime_error("haarpsi needs YUV input (Y4M, raw planar YUV or decoded video), not RGB images");
+        }
+    }
+    void push(const HwFrame &r, const HwFrame &d)
+    {
+        int lr, ld;
+        uint32_t br, bd;
+        layout_of(r, lr, br);
+        layout_of(d, ld, bd);
+        if (lr != ld || br != bd || r.device != d.device) throw std::runtime_error("haarpsi needs reference and distorted in the same YUV layout and bit depth");
+        if (!v) {
+            layout = lr; bits = br;
+            const int rc = create(&v, w, h, layout, bits, batch, map_prefix.empty() ? 0u : (uint32_t)TM_HAARPSI_MAPS);
+            if (rc == TM_ERR_UNSUPPORTED) throw std::runtime_error("haarpsi takes pictures of 4 x 4 to 32768 x 32768 samples");
+            chk(rc, "tm_haarpsi_create");
+        } else if (lr != layout || br != bits) {
+            throw std::runtime_error("haarpsi: the YUV layout changed inside the stream");
+        }
+        chk(set_pair(v, filled, r.data, d.data, r.pitch, d.pitch, r.device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_haarpsi_set_pair");
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(v, filled), "tm_haarpsi_compute_async");
+        chk(sync(v), "tm_haarpsi_sync");
+        std::vector<tm_haarpsi_frame> out(filled);
+        chk(get(v, 0, filled, out.data()), "tm_haarpsi_get");
+        const uint32_t w2 = (w + 1) / 2, h2 = (h + 1) / 2;
+        for (uint32_t i = 0; i < filled; ++i) {
+            const tm_haarpsi_frame &f = out[i];
+            ready.push_back(score(f.q, f.ws));
+            sum_q += f.q;
+            sum_ws += f.ws;
+            if (map_prefix.empty()) continue;
+            map.resize((size_t)w2 * h2);
+            chk(get_map(v, i, map.data(), (size_t)w2 * sizeof(float)), "tm_haarpsi_map");
+            char num[32];
+            snprintf(num, sizeof num, "%06zu.pfm", written++);
+            write_pfm_gray(map_prefix + num, w2, h2, map.data());
+        }
+        filled = 0;
+    }
+    double pop()
+    {
+        if (ready.empty()) throw std::logic_error("haarpsi: a pair's result is missing");
+        const double s = ready.front();
+        ready.pop_front();
+        return s;
+    }
+    double sequence_score() const { return score(sum_q, sum_ws); }
+};
+
 // ---- CIEDE2000 ---------------------------------------------------------------------------------------------------------
 // libturbometrics_ciede.so, loaded at run time like the YUV library (a CLI run without -m ciede2000 never loads it).  Pairs are handed over
 // as -m psnr-yuv hands them over and computed batch by batch in stream order; a pair's two values (kCiedeNames: the score and the mean dE00)
@@ -1414,7 +1525,8 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
     if (metrics_.psnr_hvs || metrics_.psnr_hvs_m) hv_ = std::make_unique<HvsRun>(w_, h_, batch_);
     if (metrics_.ciede) ci_ = std::make_unique<CiedeRun>(w_, h_, batch_, metrics_.ciede_libvmaf, metrics_.ciede_map);
     if (metrics_.gmsd) gm_ = std::make_unique<GmsdRun>(w_, h_, batch_, metrics_.gmsd_population, metrics_.gmsd_map);
-    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_ || hv_ || ci_ || si_ || gm_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
+    if (metrics_.haarpsi) hp_ = std::make_unique<HaarpsiRun>(w_, h_, batch_, metrics_.haarpsi_map);
+    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_ || hv_ || ci_ || si_ || gm_ || hp_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -1723,6 +1835,8 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     if (si_) { s_si.emplace(); s_ti.emplace(); }
     std::optional<std::vector<double>> s_gm[2]; // kGmsdNames
     if (gm_) { s_gm[0].emplace(); s_gm[1].emplace(); }
+    std::optional<std::vector<double>> s_hp;
+    if (hp_) s_hp.emplace();
     std::optional<FrameScores> held;
     auto emit = [&](const FrameScores &r) {
         if (on_frame) on_frame(r);
@@ -1808,6 +1922,10 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
                 const std::array<double, 2> v = gm_->pop();
                 for (int k = 0; k < 2; ++k) { r.gmsd[k] = v[k]; s_gm[k]->push_back(v[k]); }
             }
+            if (hp_) {
+                r.haarpsi = hp_->pop();
+                s_hp->push_back(*r.haarpsi);
+            }
             if (mo_) {
                 r.motion = mo_->pop();
                 if (held) {
@@ -1838,6 +1956,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (ci_) ci_->flush();
         if (si_) si_->flush();
         if (gm_) gm_->flush();
+        if (hp_) hp_->flush();
         in_flight[i] = true;
     };
 
@@ -1917,6 +2036,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (ci_) ci_->push(fref, fdis, cref, cdis);
         if (si_) si_->push(fref);
         if (gm_) gm_->push(fref, fdis);
+        if (hp_) hp_->push(fref, fdis);
         if (eng_[cur]) {
             set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
             set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
@@ -1955,7 +2075,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_ || hv_ || ci_ || si_ || gm_))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_ || hv_ || ci_ || si_ || gm_ || hp_))
         throw NoFramesSelected();
     if (xp_) {
         std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
@@ -2021,6 +2141,10 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
             res.gmsd[k] = MetricAggregate::from(std::move(*s_gm[k]));
             res.gmsd[k]->sequence = gm_->sequence_score(k);
         }
+    if (s_hp) {
+        res.haarpsi = MetricAggregate::from(std::move(*s_hp));
+        res.haarpsi->sequence = hp_->sequence_score();
+    }
     if (s_psnr) res.psnr = MetricAggregate::from(std::move(*s_psnr));
     if (s_ssim) res.ssim = MetricAggregate::from(std::move(*s_ssim));
     if (s_msssim) res.msssim = MetricAggregate::from(std::move(*s_msssim));

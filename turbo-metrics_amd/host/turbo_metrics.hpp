@@ -72,6 +72,10 @@ struct Metrics {
     // PREFIX%06d.pfm); not an engine metric
     bool gmsd = false, gmsd_population = false;
     std::string gmsd_map;
+    // HaarPSI of the luma planes (include/turbo_metrics_haarpsi.h, libturbometrics_haarpsi.so): the CLI's -m haarpsi and --haarpsi-map (a prefix:
+    // every pair's local similarity map as PREFIX%06d.pfm); not an engine metric
+    bool haarpsi = false;
+    std::string haarpsi_map;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -123,6 +127,8 @@ struct MetricsResults {
     std::optional<MetricAggregate> si, ti;
     // -m gmsd: [0] gmsd, [1] gmsm (the mean GMS); sequence: from the summed E1, E2 and N, pooled over all positions of all pairs; names: kGmsdNames
     std::optional<MetricAggregate> gmsd[2];
+    // -m haarpsi; sequence: the host function of the summed Q and WS of all pairs
+    std::optional<MetricAggregate> haarpsi;
 };
 
 struct MetricsStats {
@@ -156,6 +162,7 @@ struct FrameScores {
     std::optional<double> si, ti;   // --siti; ti_valid false: the first picture of the stream, ti is 0 and stays out of the aggregates
     bool ti_valid = false;
     std::optional<double> gmsd[2]; // kGmsdNames
+    std::optional<double> haarpsi;
 };
 
 extern const char *const kYuvNames[8];
@@ -356,6 +363,7 @@ private:
     std::unique_ptr<struct YuvRun> yv_;                       // metrics_.psnr_yuv / ssim_yuv: the YUV PSNR / SSIM library's state (likewise; no history)
     std::unique_ptr<struct CiedeRun> ci_;                     // metrics_.ciede: the CIEDE2000 library's state (likewise; no history)
     std::unique_ptr<struct GmsdRun> gm_;                      // metrics_.gmsd: the GMSD library's state (likewise; no history)
+    std::unique_ptr<struct HaarpsiRun> hp_;                   // metrics_.haarpsi: the HaarPSI library's state (likewise; no history)
     std::unique_ptr<struct HvsRun> hv_;                       // metrics_.psnr_hvs / psnr_hvs_m: the PSNR-HVS library's state (likewise; no history)
     std::unique_ptr<struct FlipRun> fl_;                      // metrics_.flip: the FLIP library's state (likewise; no history)
     std::unique_ptr<struct SceneRun> sc_;                     // metrics_.scenes: the reference stream's previous histogram (likewise)
