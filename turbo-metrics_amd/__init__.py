@@ -17,6 +17,7 @@ C ABI) with a host-side mirror of the reference's operator interface.
   siti    -- ctypes binding of include/turbo_metrics_siti.h (libturbometrics_siti.so): Siti, ITU-T P.910 spatial / temporal information of one stream
   gmsd    -- ctypes binding of include/turbo_metrics_gmsd.h (libturbometrics_gmsd.so): Gmsd, the gradient magnitude similarity deviation of the lumas of frame pairs
   haarpsi -- ctypes binding of include/turbo_metrics_haarpsi.h (libturbometrics_haarpsi.so): HaarPsi, the Haar wavelet-based perceptual similarity index of the lumas of frame pairs
+  itp     -- ctypes binding of include/turbo_metrics_itp.h (libturbometrics_itp.so): Itp, the BT.2124 colour difference dE ITP of 4:2:0 HDR (PQ / HLG) frame pairs
 
 There is no CPU implementation in this package: without the HIP library (or without a gfx950 GPU)
 the operators raise.
@@ -48,3 +49,5 @@ from . import gmsd  # noqa: F401,E402
 from .gmsd import Gmsd, GmsdFrame  # noqa: F401,E402
 from . import haarpsi  # noqa: F401,E402
 from .haarpsi import HaarPsi, HaarPsiFrame  # noqa: F401,E402
+from . import itp  # noqa: F401,E402
+from .itp import Itp, ItpFrame  # noqa: F401,E402

@@ -11,6 +11,7 @@
 #include "../../include/turbo_metrics_hvs.h"
 #include "../../include/turbo_metrics_gmsd.h"
 #include "../../include/turbo_metrics_haarpsi.h"
+#include "../../include/turbo_metrics_itp.h"
 #include "../../include/turbo_metrics_ciede.h"
 #include "frame_sources.hpp" // write_pfm_gray
 #include "../../include/turbo_metrics_vif.h"
@@ -1190,6 +1191,127 @@ struct HaarpsiRun {
     double sequence_score() const { return score(sum_q, sum_ws); }
 };
 
+// ---- dE ITP ----------------------------------------------------------------------------------------------------------------
+// libturbometrics_itp.so, loaded at run time like the CIEDE2000 library (a CLI run without -m deitp never loads it).  Pairs are handed over
+// as -m ciede2000 hands them over and computed batch by batch in stream order; a pair's two values (kItpNames: the mean and the largest
+// dE ITP) wait in `ready` until the engine's scores of the same pair are drained.  The matrix is always BT.2020 non-constant luminance: the
+// streams' matrix coefficients are not consulted; the transfer is --itp-transfer's.  The sequence values: the summed dE ITP over the summed
+// positions, and the largest maximum.  --itp-map: every pair's dE ITP map goes to PREFIX%06d.pfm, numbered in the order the pairs are
+// computed.  No history: --every is fine.
+const char *const kItpNames[2] = {"deitp", "deitp_max"};
+
+struct ItpRun {
+    void *lib = nullptr;
+    int (*create)(tm_itp **, uint32_t, uint32_t, int, uint32_t, int, int, int, uint32_t) = nullptr;
+    void (*destroy)(tm_itp *) = nullptr;
+    int (*set_frame)(tm_itp *, uint32_t, int, const void *, const void *, const void *, size_t, size_t, int) = nullptr;
+    int (*compute_async)(tm_itp *, uint32_t) = nullptr;
+    int (*sync)(tm_itp *) = nullptr;
+    int (*get)(tm_itp *, uint32_t, uint32_t, tm_itp_frame *) = nullptr;
+    int (*get_map)(tm_itp *, uint32_t, float *, size_t) = nullptr;
+    tm_itp *x = nullptr;
+    uint32_t w, h, batch;
+    bool hlg;
+    std::string map_prefix;
+    int layout = -1;
+    uint32_t bits = 8, filled = 0;
+    size_t written = 0;
+    std::vector<float> map;
+    std::deque<std::array<double, 2>> ready;
+    double sum_de = 0.0, max_de = 0.0;
+    uint64_t sum_px = 0;
+
+    ItpRun(uint32_t w_, uint32_t h_, uint32_t batch_, bool hlg_, std::string prefix) : w(w_), h(h_), batch(batch_), hlg(hlg_), map_prefix(std::move(prefix))
+    {
+        const char *path = getenv("TM_ITP_LIB");
+        lib = dlopen(path ? path : "libturbometrics_itp.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("-m deitp needs libturbometrics_itp.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_itp_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_itp_destroy");
+        set_frame = (decltype(set_frame))dlsym(lib, "tm_itp_set_frame");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_itp_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_itp_sync");
+        get = (decltype(get))dlsym(lib, "tm_itp_get");
+        get_map = (decltype(get_map))dlsym(lib, "tm_itp_get_map");
+        if (!create || !destroy || !set_frame || !compute_async || !sync || !get || !get_map) {
+            dlclose(lib); // the destructor does not run for an object whose constructor throws
+            throw std::runtime_error("libturbometrics_itp.so does not export include/turbo_metrics_itp.h");
+        }
+    }
+    ~ItpRun()
+    {
+        if (x) destroy(x);
+        if (lib) dlclose(lib);
+    }
+    static void layout_of(const HwFrame &f, int &layout, uint32_t &bits)
+    {
+        switch (f.kind) {
+        case HwFrame::NvDecNV12: layout = TM_ITP_NV12; bits = 8; return;
+        case HwFrame::NvDecP016: layout = TM_ITP_P016; bits = 10; return;
+        case HwFrame::Planar420: layout = TM_ITP_I420; bits = (uint32_t)f.bits; return;
+        case HwFrame::Planar420P10: layout = TM_ITP_I420P10_PACKED; bits = 10; return;
+        default: throw std::runtime_error("deitp needs 4:2:0 YUV input (Y4M, raw planar YUV or decoded video), not RGB images");
+        }
+    }
+    using ColorInfo = TurboMetrics::ColorInfo;
+    void push(const HwFrame &r, const HwFrame &d, const ColorInfo &cr, const ColorInfo &cd)
+    {
+        int lr, ld;
+        uint32_t br, bd;
+        layout_of(r, lr, br);
+        layout_of(d, ld, bd);
+        if (lr != ld || br != bd) throw std::runtime_error("deitp needs reference and distorted in the same YUV layout and bit depth");
+        if (cr.second == ColorRange::Full || cd.second == ColorRange::Full) throw std::runtime_error("deitp takes limited-range YUV only");
+        if (!x) {
+            layout = lr; bits = br;
+            const int rc = create(&x, w, h, layout, bits, hlg ? TM_ITP_HLG : TM_ITP_PQ, 0, map_prefix.empty() ? 0 : 1, batch);
+            if (rc == TM_ERR_UNSUPPORTED) throw std::runtime_error("deitp takes pictures of 2 x 2 to 32768 x 32768 samples");
+            chk(rc, "tm_itp_create");
+        } else if (lr != layout || br != bits) {
+            throw std::runtime_error("deitp: the YUV layout changed inside the stream");
+        }
+        const bool bi = layout == TM_ITP_NV12 || layout == TM_ITP_P016;
+        int side = TM_SIDE_REF;
+        for (const HwFrame *f : {&r, &d}) {
+            chk(set_frame(x, filled, side, f->data, bi ? f->uv : f->u, bi ? nullptr : f->v, f->pitch, bi ? f->pitch : f->pitch_uv,
+                          f->device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_itp_set_frame");
+            side = TM_SIDE_DIS;
+        }
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(x, filled), "tm_itp_compute_async");
+        chk(sync(x), "tm_itp_sync");
+        std::vector<tm_itp_frame> out(filled);
+        chk(get(x, 0, filled, out.data()), "tm_itp_get");
+        for (uint32_t i = 0; i < filled; ++i) {
+            const tm_itp_frame &f = out[i];
+            ready.push_back({f.de_mean, f.de_max});
+            sum_de += f.de_sum;
+            sum_px += f.pixels;
+            max_de = std::max(max_de, f.de_max);
+            if (map_prefix.empty()) continue;
+            map.resize((size_t)w * h);
+            chk(get_map(x, i, map.data(), (size_t)w * sizeof(float)), "tm_itp_get_map");
+            char num[32];
+            snprintf(num, sizeof num, "%06zu.pfm", written++);
+            write_pfm_gray(map_prefix + num, w, h, map.data());
+        }
+        filled = 0;
+    }
+    std::array<double, 2> pop()
+    {
+        if (ready.empty()) throw std::logic_error("deitp: a pair's result is missing");
+        const std::array<double, 2> v = ready.front();
+        ready.pop_front();
+        return v;
+    }
+    // the sequence value of column k (kItpNames)
+    double sequence_score(int k) const { return k ? max_de : sum_de / (double)sum_px; }
+};
+
 // ---- CIEDE2000 ---------------------------------------------------------------------------------------------------------
 // libturbometrics_ciede.so, loaded at run time like the YUV library (a CLI run without -m ciede2000 never loads it).  Pairs are handed over
 // as -m psnr-yuv hands them over and computed batch by batch in stream order; a pair's two values (kCiedeNames: the score and the mean dE00)
@@ -1526,7 +1648,8 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
     if (metrics_.ciede) ci_ = std::make_unique<CiedeRun>(w_, h_, batch_, metrics_.ciede_libvmaf, metrics_.ciede_map);
     if (metrics_.gmsd) gm_ = std::make_unique<GmsdRun>(w_, h_, batch_, metrics_.gmsd_population, metrics_.gmsd_map);
     if (metrics_.haarpsi) hp_ = std::make_unique<HaarpsiRun>(w_, h_, batch_, metrics_.haarpsi_map);
-    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_ || hv_ || ci_ || si_ || gm_ || hp_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
+    if (metrics_.deitp) it_ = std::make_unique<ItpRun>(w_, h_, batch_, metrics_.itp_hlg, metrics_.itp_map);
+    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_ || hv_ || ci_ || si_ || gm_ || hp_ || it_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -1837,6 +1960,8 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     if (gm_) { s_gm[0].emplace(); s_gm[1].emplace(); }
     std::optional<std::vector<double>> s_hp;
     if (hp_) s_hp.emplace();
+    std::optional<std::vector<double>> s_it[2]; // kItpNames
+    if (it_) { s_it[0].emplace(); s_it[1].emplace(); }
     std::optional<FrameScores> held;
     auto emit = [&](const FrameScores &r) {
         if (on_frame) on_frame(r);
@@ -1926,6 +2051,10 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
                 r.haarpsi = hp_->pop();
                 s_hp->push_back(*r.haarpsi);
             }
+            if (it_) {
+                const std::array<double, 2> v = it_->pop();
+                for (int k = 0; k < 2; ++k) { r.deitp[k] = v[k]; s_it[k]->push_back(v[k]); }
+            }
             if (mo_) {
                 r.motion = mo_->pop();
                 if (held) {
@@ -1957,6 +2086,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (si_) si_->flush();
         if (gm_) gm_->flush();
         if (hp_) hp_->flush();
+        if (it_) it_->flush();
         in_flight[i] = true;
     };
 
@@ -2037,6 +2167,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (si_) si_->push(fref);
         if (gm_) gm_->push(fref, fdis);
         if (hp_) hp_->push(fref, fdis);
+        if (it_) it_->push(fref, fdis, cref, cdis);
         if (eng_[cur]) {
             set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
             set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
@@ -2075,7 +2206,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_ || hv_ || ci_ || si_ || gm_ || hp_))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_ || hv_ || ci_ || si_ || gm_ || hp_ || it_))
         throw NoFramesSelected();
     if (xp_) {
         std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
@@ -2145,6 +2276,11 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         res.haarpsi = MetricAggregate::from(std::move(*s_hp));
         res.haarpsi->sequence = hp_->sequence_score();
     }
+    if (it_)
+        for (int k = 0; k < 2; ++k) {
+            res.deitp[k] = MetricAggregate::from(std::move(*s_it[k]));
+            res.deitp[k]->sequence = it_->sequence_score(k);
+        }
     if (s_psnr) res.psnr = MetricAggregate::from(std::move(*s_psnr));
     if (s_ssim) res.ssim = MetricAggregate::from(std::move(*s_ssim));
     if (s_msssim) res.msssim = MetricAggregate::from(std::move(*s_msssim));

@@ -76,6 +76,10 @@ struct Metrics {
     // every pair's local similarity map as PREFIX%06d.pfm); not an engine metric
     bool haarpsi = false;
     std::string haarpsi_map;
+    // dE ITP (BT.2124) of 4:2:0 HDR pairs (include/turbo_metrics_itp.h, libturbometrics_itp.so): the CLI's -m deitp, --itp-transfer (pq | hlg) and
+    // --itp-map (a prefix: every pair's dE ITP map as PREFIX%06d.pfm); not an engine metric
+    bool deitp = false, itp_hlg = false;
+    std::string itp_map;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -129,6 +133,8 @@ struct MetricsResults {
     std::optional<MetricAggregate> gmsd[2];
     // -m haarpsi; sequence: the host function of the summed Q and WS of all pairs
     std::optional<MetricAggregate> haarpsi;
+    // -m deitp: [0] deitp (the pair's mean dE ITP), [1] deitp_max; sequence: the summed dE ITP over the summed positions, the largest maximum; names: kItpNames
+    std::optional<MetricAggregate> deitp[2];
 };
 
 struct MetricsStats {
@@ -163,12 +169,14 @@ struct FrameScores {
     bool ti_valid = false;
     std::optional<double> gmsd[2]; // kGmsdNames
     std::optional<double> haarpsi;
+    std::optional<double> deitp[2]; // kItpNames
 };
 
 extern const char *const kYuvNames[8];
 extern const char *const kHvsNames[2];
 extern const char *const kGmsdNames[2];
 extern const char *const kCiedeNames[2];
+extern const char *const kItpNames[2];
 
 // ---- colour metadata (H.273 code points the reference understands, codec-bitstream/src/lib.rs:98-248) ----------
 enum class ColourPrimaries { Invalid, Unspecified, Unsupported, BT709, BT601_525, BT601_625 };
@@ -363,6 +371,7 @@ private:
     std::unique_ptr<struct YuvRun> yv_;                       // metrics_.psnr_yuv / ssim_yuv: the YUV PSNR / SSIM library's state (likewise; no history)
     std::unique_ptr<struct CiedeRun> ci_;                     // metrics_.ciede: the CIEDE2000 library's state (likewise; no history)
     std::unique_ptr<struct GmsdRun> gm_;                      // metrics_.gmsd: the GMSD library's state (likewise; no history)
+    std::unique_ptr<struct ItpRun> it_;                       // metrics_.deitp: the dE ITP library's state (likewise; no history)
     std::unique_ptr<struct HaarpsiRun> hp_;                   // metrics_.haarpsi: the HaarPSI library's state (likewise; no history)
     std::unique_ptr<struct HvsRun> hv_;                       // metrics_.psnr_hvs / psnr_hvs_m: the PSNR-HVS library's state (likewise; no history)
     std::unique_ptr<struct FlipRun> fl_;                      // metrics_.flip: the FLIP library's state (likewise; no history)
