@@ -18,6 +18,7 @@ C ABI) with a host-side mirror of the reference's operator interface.
   gmsd    -- ctypes binding of include/turbo_metrics_gmsd.h (libturbometrics_gmsd.so): Gmsd, the gradient magnitude similarity deviation of the lumas of frame pairs
   haarpsi -- ctypes binding of include/turbo_metrics_haarpsi.h (libturbometrics_haarpsi.so): HaarPsi, the Haar wavelet-based perceptual similarity index of the lumas of frame pairs
   itp     -- ctypes binding of include/turbo_metrics_itp.h (libturbometrics_itp.so): Itp, the BT.2124 colour difference dE ITP of 4:2:0 HDR (PQ / HLG) frame pairs
+  mdsi    -- ctypes binding of include/turbo_metrics_mdsi.h (libturbometrics_mdsi.so): Mdsi, the mean deviation similarity index (gradient and chromaticity similarity, deviation pooling) of 4:2:0 frame pairs
 
 There is no CPU implementation in this package: without the HIP library (or without a gfx950 GPU)
 the operators raise.
@@ -51,3 +52,5 @@ from . import haarpsi  # noqa: F401,E402
 from .haarpsi import HaarPsi, HaarPsiFrame  # noqa: F401,E402
 from . import itp  # noqa: F401,E402
 from .itp import Itp, ItpFrame  # noqa: F401,E402
+from . import mdsi  # noqa: F401,E402
+from .mdsi import Mdsi, MdsiFrame  # noqa: F401,E402

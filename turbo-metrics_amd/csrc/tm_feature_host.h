@@ -1,4 +1,4 @@
-// tm_feature_host.h -- the host core the fourteen feature libraries share (tm_xpsnr.hip ... tm_itp.hip): the state
+// tm_feature_host.h -- the host core the fifteen feature libraries share (tm_xpsnr.hip ... tm_mdsi.hip): the state
 // every handle carries, create / destroy plumbing, the staging upload of host pictures and the set -> compute_async -> sync -> get
 // state machine.  Host code only: a plain struct and free functions, no kernels and no entry points -- every library keeps its own
 // create, set_*, compute_async and get, and embeds TmFeatureHost as the member `c`.  tests/host/feature_host_test.cpp compiles this

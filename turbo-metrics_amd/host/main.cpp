@@ -53,6 +53,7 @@ void usage(std::ostream &os)
           "                             [and: gmsd]\n"
           "                             [and: haarpsi]\n"
           "                             [and: deitp]\n"
+          "                             [and: mdsi]\n"
           "                             and vif: VMAF's VIF of the luma planes, four scales (YUV inputs; runs beside the others or alone)\n"
           "                             and adm: VMAF's ADM of the luma planes, adm2 and four scales (likewise)\n"
           "      --every <EVERY>        Only compute metrics every few frames [default: 0]\n"
@@ -122,6 +123,14 @@ void usage(std::ostream &os)
           "                             alone or beside the other -m values\n"
           "      --itp-transfer <pq|hlg>  the transfer function of the samples: BT.2100 PQ, or HLG on a 1000 cd/m2 display (with -m deitp) [default: pq]\n"
           "      --itp-map <PREFIX>     write every pair's dE ITP map as a one-channel PFM, PREFIX000000.pfm, PREFIX000001.pfm, ... (with -m deitp)\n"
+          "  -m mdsi                    MDSI, the mean deviation similarity index, of 4:2:0 YUV pairs: gradient similarity of the luma-like plane and\n"
+          "                             chromaticity similarity at every f-th position of the f x f box mean, pooled by the mean absolute deviation of the\n"
+          "                             fourth roots (0: identical; larger is worse).  Limited range; the matrix follows --matrix-coefficients as for\n"
+          "                             ciede2000.  Prints mdsi after all other columns.  MDSI does not pool across pictures: the sequence value is the\n"
+          "                             mean of the per-pair values; alone or beside the other -m values\n"
+          "      --mdsi-factor <N>      the decimation factor f, 1 ... 128 (with -m mdsi) [default: max(1, round(min(width, height) / 256))]\n"
+          "      --mdsi-map <PREFIX>    write every pair's GCS map (ceil(height / f) rows of ceil(width / f)) as a one-channel PFM, PREFIX000000.pfm, ...\n"
+          "                             (with -m mdsi)\n"
           "      --psnr-yuv-cap         cap every PSNR at libvmaf's 6 * depth + 12 dB instead of printing inf (with -m psnr-yuv)\n"
           "      --ssim-yuv-map <PREFIX>  write every pair's luma SSIM window map as a one-channel PFM, PREFIX000000.pfm, ... (with -m ssim-yuv)\n"
           "      --cambi-window <N>     side of the window the banding is looked for in, 3 ... 127 (with -m cambi) [default: 63 * width / 3840, at least 3]\n"
@@ -193,7 +202,7 @@ int main(int argc, char **argv)
     uint32_t batch = 0 /* 0: chosen from the picture size */, device = 0, devices = 1, ranks = 0 /* 0: not asked for */, in_flight_pairs = 2;
     uint32_t xpsnr_fps_num = 0, xpsnr_fps_den = 1; // --xpsnr-fps (0: not given)
     bool pipeline = true, full_sums = false, in_flight_given = false, scene_values_given = false, cambi_values_given = false, flip_values_given = false, siti_gain_given = false, siti_range_given = false, siti_limited = false;
-    bool psnr_yuv_values_given = false, ssim_yuv_values_given = false, ciede_values_given = false, gmsd_values_given = false, haarpsi_values_given = false, itp_values_given = false;
+    bool psnr_yuv_values_given = false, ssim_yuv_values_given = false, ciede_values_given = false, gmsd_values_given = false, haarpsi_values_given = false, itp_values_given = false, mdsi_values_given = false;
     enum class Loop { Batched, Reference, Deferred } loop = Loop::Batched;
     std::vector<std::pair<int, long long>> tune;
 
@@ -238,7 +247,8 @@ int main(int argc, char **argv)
             else if (s == "gmsd") metrics.gmsd = true;
             else if (s == "haarpsi") metrics.haarpsi = true;
             else if (s == "deitp") metrics.deitp = true;
-            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv, psnr-hvs, psnr-hvs-m] [and: ciede2000] [and: gmsd] [and: haarpsi] [and: deitp]");
+            else if (s == "mdsi") metrics.mdsi = true;
+            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv, psnr-hvs, psnr-hvs-m] [and: ciede2000] [and: gmsd] [and: haarpsi] [and: deitp] [and: mdsi]");
         } else if (a.rfind("-m", 0) == 0 && a.size() > 2 && a[1] == 'm') { // -mpsnr
             const std::string s = a.substr(2);
             if (s == "psnr") metrics.psnr = true; else if (s == "ssim") metrics.ssim = true; else if (s == "msssim") metrics.msssim = true;
@@ -256,7 +266,8 @@ int main(int argc, char **argv)
             else if (s == "gmsd") metrics.gmsd = true;
             else if (s == "haarpsi") metrics.haarpsi = true;
             else if (s == "deitp") metrics.deitp = true;
-            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv, psnr-hvs, psnr-hvs-m] [and: ciede2000] [and: gmsd] [and: haarpsi] [and: deitp]");
+            else if (s == "mdsi") metrics.mdsi = true;
+            else return bad("invalid value '" + s + "' for '--metrics <METRICS>'\n  [possible values: psnr, ssim, msssim, ssimulacra2, xpsnr, vif, adm, cambi, flip, psnr-yuv, ssim-yuv, psnr-hvs, psnr-hvs-m] [and: ciede2000] [and: gmsd] [and: haarpsi] [and: deitp] [and: mdsi]");
         } else if (a == "--every") { if (!u32(opts.every)) return bad("invalid value for '--every <EVERY>'"); }
         else if (a == "--skip") { if (!u32(opts.skip)) return bad("invalid value for '--skip <SKIP>'"); }
         else if (a == "--skip-ref") { if (!u32(opts.skip_ref)) return bad("invalid value for '--skip-ref <SKIP_REF>'"); }
@@ -371,6 +382,14 @@ int main(int argc, char **argv)
             metrics.itp_hlg = v == "hlg";
             itp_values_given = true;
         }
+        else if (a == "--mdsi-factor") {
+            if (!u32(metrics.mdsi_factor) || metrics.mdsi_factor < 1 || metrics.mdsi_factor > 128) return bad("invalid value for '--mdsi-factor <N>' (1 ... 128)");
+            mdsi_values_given = true;
+        }
+        else if (a == "--mdsi-map") {
+            if (!value(metrics.mdsi_map) || metrics.mdsi_map.empty()) return bad("a value is required for '--mdsi-map <PREFIX>' but none was supplied");
+            mdsi_values_given = true;
+        }
         else if (a == "--itp-map") {
             if (!value(metrics.itp_map) || metrics.itp_map.empty()) return bad("a value is required for '--itp-map <PREFIX>' but none was supplied");
             itp_values_given = true;
@@ -428,6 +447,11 @@ int main(int argc, char **argv)
         if (why) { log_line(L_ERROR, kTarget, std::string("-m haarpsi does not run with ") + why); return EXIT_FAILURE; }
     }
     if (itp_values_given && !metrics.deitp) return bad("'--itp-transfer <pq|hlg>' and '--itp-map <PREFIX>' belong to '-m deitp'");
+    if (mdsi_values_given && !metrics.mdsi) return bad("'--mdsi-factor <N>' and '--mdsi-map <PREFIX>' belong to '-m mdsi'");
+    if (metrics.mdsi) { // like -m ciede2000: one device, the batched loop
+        const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
+        if (why) { log_line(L_ERROR, kTarget, std::string("-m mdsi does not run with ") + why); return EXIT_FAILURE; }
+    }
     if (metrics.deitp) { // like -m ciede2000: one device, the batched loop
         const char *why = devices != 1 ? "--devices" : ranks > 0 ? "--ranks" : loop != Loop::Batched ? "--loop reference / deferred" : nullptr;
         if (why) { log_line(L_ERROR, kTarget, std::string("-m deitp does not run with ") + why); return EXIT_FAILURE; }
@@ -730,7 +754,7 @@ int main(int argc, char **argv)
 
     std::unique_ptr<TurboMetrics> turbo;
     try {
-        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi && !metrics.flip && !metrics.psnr_yuv && !metrics.ssim_yuv && !metrics.psnr_hvs && !metrics.psnr_hvs_m && !metrics.ciede && !metrics.siti && !metrics.gmsd && !metrics.haarpsi && !metrics.deitp) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
+        if (metrics.mask() == 0 && !metrics.xpsnr && !metrics.motion && !metrics.vif && !metrics.adm && !metrics.scenes && !metrics.cambi && !metrics.flip && !metrics.psnr_yuv && !metrics.ssim_yuv && !metrics.psnr_hvs && !metrics.psnr_hvs_m && !metrics.ciede && !metrics.siti && !metrics.gmsd && !metrics.haarpsi && !metrics.deitp && !metrics.mdsi) throw std::runtime_error("no metric selected (-m psnr|ssim|msssim|ssimulacra2)");
         // a source that knows its length never needs more slots than it has pairs (a single image pair: one slot, one engine)
         const size_t known = std::min(source_ref->frame_count(), source_dis->frame_count());
         if (batch == 0) batch = auto_batch(source_ref->width(), source_ref->height());

@@ -30,7 +30,8 @@ std::vector<Named> stat_fields(const Stats &s)
 
 void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os, bool xpsnr = false, bool motion = false, bool vif = false, bool adm = false,
                 bool scene = false, bool cambi = false, bool cambi_ref = false, bool flip = false, bool psnr_yuv = false, bool ssim_yuv = false, bool psnr_hvs = false,
-                bool psnr_hvs_m = false, bool ciede = false, bool siti = false, bool gmsd = false, bool haarpsi = false, bool deitp = false)
+                bool psnr_hvs_m = false, bool ciede = false, bool siti = false, bool gmsd = false, bool haarpsi = false, bool deitp = false,
+                bool mdsi = false)
 {
     bool first = true;
     auto put = [&](bool on, const char *n) { if (on) { os << (first ? "" : ",") << n; first = false; } };
@@ -50,6 +51,7 @@ void csv_header(bool psnr, bool ssim, bool msssim, bool ssimu, std::ostream &os,
     put(gmsd, kGmsdNames[0]); put(gmsd, kGmsdNames[1]);
     put(haarpsi, "haarpsi");
     put(deitp, kItpNames[0]); put(deitp, kItpNames[1]);
+    put(mdsi, "mdsi");
     if (first) os << "\"\""; // csv::Writer writes an empty record as ""
     os << "\n";
 }
@@ -63,7 +65,8 @@ void csv_row(const std::optional<double> &a, const std::optional<double> &b, con
              const std::optional<double> *cambi_ref6 = nullptr, const std::optional<double> *flip3 = nullptr, const std::optional<double> *yuv8 = nullptr,
              const std::optional<double> *hvs2 = nullptr, const std::optional<double> *ciede2 = nullptr, const std::optional<double> &si = std::nullopt,
              const std::optional<double> &ti = std::nullopt, const std::optional<double> *gmsd2 = nullptr,
-             const std::optional<double> &haarpsi = std::nullopt, const std::optional<double> *deitp2 = nullptr)
+             const std::optional<double> &haarpsi = std::nullopt, const std::optional<double> *deitp2 = nullptr,
+             const std::optional<double> &mdsi = std::nullopt)
 {
     bool first = true;
     auto put = [&](const std::optional<double> &v) { if (v) { os << (first ? "" : ",") << display(*v); first = false; } };
@@ -92,6 +95,7 @@ void csv_row(const std::optional<double> &a, const std::optional<double> &b, con
     put(haarpsi);
     if (deitp2)
         for (int k = 0; k < 2; ++k) put(deitp2[k]);
+    put(mdsi);
     if (first) os << "\"\"";
     os << "\n";
 }
@@ -136,6 +140,7 @@ std::string frame_scores_json(const FrameScores &r)
     for (int k = 0; k < 2; ++k) put(kGmsdNames[k], r.gmsd[k]);
     put("haarpsi", r.haarpsi);
     for (int k = 0; k < 2; ++k) put(kItpNames[k], r.deitp[k]);
+    put("mdsi", r.mdsi);
     return s + "}";
 }
 
@@ -166,7 +171,7 @@ std::string stats_json(const Stats &s, int indent, bool pretty)
 void output_prepare(Output o, const Metrics &m, std::ostream &os)
 {
     if (o == Output::CSV) csv_header(m.psnr, m.ssim, m.msssim, m.ssimulacra2, os, m.xpsnr, m.motion, m.vif, m.adm, m.scenes, m.cambi, m.cambi && m.cambi_ref, m.flip, m.psnr_yuv, m.ssim_yuv,
-                                     m.psnr_hvs, m.psnr_hvs_m, m.ciede, m.siti, m.gmsd, m.haarpsi, m.deitp);
+                                     m.psnr_hvs, m.psnr_hvs_m, m.ciede, m.siti, m.gmsd, m.haarpsi, m.deitp, m.mdsi);
 }
 
 void output_single_score(Output o, const FrameScores &r, std::ostream &os)
@@ -178,7 +183,7 @@ void output_single_score(Output o, const FrameScores &r, std::ostream &os)
         const std::optional<double> c6[6] = {r.cambi, r.cambi_scale[0], r.cambi_scale[1], r.cambi_scale[2], r.cambi_scale[3], r.cambi_scale[4]};
         const std::optional<double> r6[6] = {r.cambi_ref, r.cambi_ref_scale[0], r.cambi_ref_scale[1], r.cambi_ref_scale[2], r.cambi_ref_scale[3], r.cambi_ref_scale[4]};
         const std::optional<double> f3[3] = {r.flip, r.flip_min, r.flip_max};
-        csv_row(r.psnr, r.ssim, r.msssim, r.ssimulacra2, os, r.xpsnr_y, r.xpsnr_u, r.xpsnr_v, r.motion, r.motion2, v5, a5, r.scene_score, r.scene_cut, c6, r6, f3, r.yuv, r.hvs, r.ciede, r.si, r.ti, r.gmsd, r.haarpsi, r.deitp);
+        csv_row(r.psnr, r.ssim, r.msssim, r.ssimulacra2, os, r.xpsnr_y, r.xpsnr_u, r.xpsnr_v, r.motion, r.motion2, v5, a5, r.scene_score, r.scene_cut, c6, r6, f3, r.yuv, r.hvs, r.ciede, r.si, r.ti, r.gmsd, r.haarpsi, r.deitp, r.mdsi);
     }
 }
 
@@ -263,6 +268,10 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
             os << (k ? "DEITP_MAX: " : "DEITP: ") << stats_debug_pretty(r.deitp[k]->stats) << "\n";
             os << (k ? "dE ITP max (sequence): " : "dE ITP mean (sequence): ") << debug(*r.deitp[k]->sequence) << "\n";
         }
+        if (r.mdsi) { // the sequence value is the mean of the pairs' values
+            os << "MDSI: " << stats_debug_pretty(r.mdsi->stats) << "\n";
+            os << "MDSI (sequence): " << debug(*r.mdsi->sequence) << "\n";
+        }
         break;
     case Output::Json: { // serde_json::to_string_pretty: two-space indent, `"key": value`
         os << "{\n  \"frame_count\": " << r.frame_count;
@@ -299,6 +308,7 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
         for (int k = 0; k < 2; ++k) put(kGmsdNames[k], r.gmsd[k]);
         put("haarpsi", r.haarpsi);
         for (int k = 0; k < 2; ++k) put(kItpNames[k], r.deitp[k]);
+        put("mdsi", r.mdsi);
         os << "\n}\n";
         break;
     }
@@ -347,12 +357,13 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
         for (int k = 0; k < 2; ++k) put_x(kGmsdNames[k], r.gmsd[k]);
         put_x("haarpsi", r.haarpsi);
         for (int k = 0; k < 2; ++k) put_x(kItpNames[k], r.deitp[k]);
+        put_x("mdsi", r.mdsi);
         os << "}\n";
         break;
     }
     case Output::CSV:
         csv_header((bool)r.psnr, (bool)r.ssim, (bool)r.msssim, (bool)r.ssimulacra2, os, (bool)r.xpsnr_y, (bool)r.motion, (bool)r.vif, (bool)r.adm2, (bool)r.scene_score, (bool)r.cambi, (bool)r.cambi_ref, (bool)r.flip, (bool)r.yuv[0], (bool)r.yuv[4],
-                   (bool)r.hvs[0], (bool)r.hvs[1], (bool)r.ciede[0], (bool)r.si, (bool)r.gmsd[0], (bool)r.haarpsi, (bool)r.deitp[0]);
+                   (bool)r.hvs[0], (bool)r.hvs[1], (bool)r.ciede[0], (bool)r.si, (bool)r.gmsd[0], (bool)r.haarpsi, (bool)r.deitp[0], (bool)r.mdsi);
         for (size_t i = 0, starts = 0; i < r.frame_count; ++i) {
             auto at = [&](const std::optional<MetricAggregate> &a) { return a ? std::optional<double>(a->scores[i]) : std::nullopt; };
             const std::optional<double> v5[5] = {at(r.vif_scale[0]), at(r.vif_scale[1]), at(r.vif_scale[2]), at(r.vif_scale[3]), at(r.vif)};
@@ -367,7 +378,7 @@ void output_results(Output o, const MetricsResults &r, std::ostream &os)
             const std::optional<double> y8[8] = {at(r.yuv[0]), at(r.yuv[1]), at(r.yuv[2]), at(r.yuv[3]), at(r.yuv[4]), at(r.yuv[5]), at(r.yuv[6]), at(r.yuv[7])};
             csv_row(at(r.psnr), at(r.ssim), at(r.msssim), at(r.ssimulacra2), os, at(r.xpsnr_y), at(r.xpsnr_u), at(r.xpsnr_v), at(r.motion), at(r.motion2), v5, a5,
                     at(r.scene_score), r.scene_score ? std::optional<bool>(i > 0 && starts < r.scene_starts.size() && r.scene_starts[starts] == i) : std::nullopt, c6, r6, f3, y8, h2, e2,
-                    at(r.si), at(r.ti), g2, at(r.haarpsi), t2);
+                    at(r.si), at(r.ti), g2, at(r.haarpsi), t2, at(r.mdsi));
             if (starts < r.scene_starts.size() && r.scene_starts[starts] == i) ++starts; // (frame 0 starts the first scene and is no cut)
         }
         break;

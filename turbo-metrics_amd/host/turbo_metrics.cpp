@@ -12,6 +12,7 @@
 #include "../../include/turbo_metrics_gmsd.h"
 #include "../../include/turbo_metrics_haarpsi.h"
 #include "../../include/turbo_metrics_itp.h"
+#include "../../include/turbo_metrics_mdsi.h"
 #include "../../include/turbo_metrics_ciede.h"
 #include "frame_sources.hpp" // write_pfm_gray
 #include "../../include/turbo_metrics_vif.h"
@@ -1312,6 +1313,137 @@ struct ItpRun {
     double sequence_score(int k) const { return k ? max_de : sum_de / (double)sum_px; }
 };
 
+// ---- MDSI ----------------------------------------------------------------------------------------------------------------
+// libturbometrics_mdsi.so, loaded at run time like the CIEDE2000 library (a CLI run without -m mdsi never loads it).  Pairs are handed over
+// as -m ciede2000 hands them over, with its rule for the matrix (the streams' matrix coefficients: BT.709 or BT.601, limited range), and
+// computed batch by batch in stream order; a pair's value waits in `ready` until the engine's scores of the same pair are drained.  MDSI
+// does not pool across pictures: the sequence value is the mean of the pairs' values.  --mdsi-map: every pair's GCS map goes to
+// PREFIX%06d.pfm, numbered in the order the pairs are computed.  No history: --every is fine.
+struct MdsiRun {
+    void *lib = nullptr;
+    int (*create)(tm_mdsi **, uint32_t, uint32_t, int, uint32_t, int, uint32_t, uint32_t, uint32_t) = nullptr;
+    void (*destroy)(tm_mdsi *) = nullptr;
+    int (*set_frame)(tm_mdsi *, uint32_t, int, const void *, const void *, const void *, size_t, size_t, int) = nullptr;
+    int (*compute_async)(tm_mdsi *, uint32_t) = nullptr;
+    int (*sync)(tm_mdsi *) = nullptr;
+    int (*get)(tm_mdsi *, uint32_t, uint32_t, tm_mdsi_frame *) = nullptr;
+    int (*get_map)(tm_mdsi *, uint32_t, float *, size_t) = nullptr;
+    double (*score)(double, uint64_t) = nullptr;
+    tm_mdsi *x = nullptr;
+    uint32_t w, h, batch, factor;
+    std::string map_prefix;
+    int layout = -1, matrix = -1;
+    uint32_t bits = 8, filled = 0;
+    size_t written = 0;
+    std::vector<float> map;
+    std::deque<double> ready;
+    double sum = 0.0;
+    uint64_t pairs = 0;
+
+    MdsiRun(uint32_t w_, uint32_t h_, uint32_t batch_, uint32_t factor_, std::string prefix) : w(w_), h(h_), batch(batch_), factor(factor_), map_prefix(std::move(prefix))
+    {
+        const char *path = getenv("TM_MDSI_LIB");
+        lib = dlopen(path ? path : "libturbometrics_mdsi.so", RTLD_NOW | RTLD_LOCAL);
+        if (!lib) throw std::runtime_error(std::string("-m mdsi needs libturbometrics_mdsi.so: ") + dlerror());
+        create = (decltype(create))dlsym(lib, "tm_mdsi_create");
+        destroy = (decltype(destroy))dlsym(lib, "tm_mdsi_destroy");
+        set_frame = (decltype(set_frame))dlsym(lib, "tm_mdsi_set_frame");
+        compute_async = (decltype(compute_async))dlsym(lib, "tm_mdsi_compute_async");
+        sync = (decltype(sync))dlsym(lib, "tm_mdsi_sync");
+        get = (decltype(get))dlsym(lib, "tm_mdsi_get");
+        get_map = (decltype(get_map))dlsym(lib, "tm_mdsi_map");
+        score = (decltype(score))dlsym(lib, "tm_mdsi_score");
+        if (!create || !destroy || !set_frame || !compute_async || !sync || !get || !get_map || !score) {
+            dlclose(lib); // the destructor does not run for an object whose constructor throws
+            throw std::runtime_error("libturbometrics_mdsi.so does not export include/turbo_metrics_mdsi.h");
+        }
+    }
+    ~MdsiRun()
+    {
+        if (x) destroy(x);
+        if (lib) dlclose(lib);
+    }
+    static void layout_of(const HwFrame &f, int &layout, uint32_t &bits)
+    {
+        switch (f.kind) {
+        case HwFrame::NvDecNV12: layout = TM_MDSI_NV12; bits = 8; return;
+        case HwFrame::NvDecP016: layout = TM_MDSI_P016; bits = 10; return;
+        case HwFrame::Planar420: layout = TM_MDSI_I420; bits = (uint32_t)f.bits; return;
+        case HwFrame::Planar420P10: layout = TM_MDSI_I420P10_PACKED; bits = 10; return;
+        default: throw std::runtime_error("mdsi needs 4:2:0 YUV input (Y4M, raw planar YUV or decoded video), not RGB images");
+        }
+    }
+    // the library's matrix for a stream's colour metadata
+    using ColorInfo = TurboMetrics::ColorInfo;
+    int matrix_of(const ColorInfo &c) const
+    {
+        if (c.second == ColorRange::Full) throw std::runtime_error("mdsi takes limited-range YUV only");
+        switch (c.first.mc) {
+        case MatrixCoefficients::BT709: return TM_MDSI_BT709;
+        case MatrixCoefficients::BT601_525: case MatrixCoefficients::BT601_625: return TM_MDSI_BT601;
+        default: throw std::runtime_error(std::string("mdsi: not implemented: matrix coefficients ") + to_string(c.first.mc));
+        }
+    }
+    void push(const HwFrame &r, const HwFrame &d, const ColorInfo &cr, const ColorInfo &cd)
+    {
+        int lr, ld;
+        uint32_t br, bd;
+        layout_of(r, lr, br);
+        layout_of(d, ld, bd);
+        if (lr != ld || br != bd) throw std::runtime_error("mdsi needs reference and distorted in the same YUV layout and bit depth");
+        const int mr = matrix_of(cr), md = matrix_of(cd);
+        if (mr != md) throw std::runtime_error("mdsi needs reference and distorted with the same matrix coefficients");
+        if (!x) {
+            layout = lr; bits = br; matrix = mr;
+            const int rc = create(&x, w, h, layout, bits, matrix, factor, map_prefix.empty() ? 0u : (uint32_t)TM_MDSI_MAPS, batch);
+            if (rc == TM_ERR_UNSUPPORTED) throw std::runtime_error("mdsi takes pictures of 2 x 2 to 32768 x 32768 samples with at least four positions after the decimation by its factor");
+            chk(rc, "tm_mdsi_create");
+        } else if (lr != layout || br != bits || mr != matrix) {
+            throw std::runtime_error("mdsi: the YUV layout or the matrix changed inside the stream");
+        }
+        const bool bi = layout == TM_MDSI_NV12 || layout == TM_MDSI_P016;
+        int side = TM_SIDE_REF;
+        for (const HwFrame *f : {&r, &d}) {
+            chk(set_frame(x, filled, side, f->data, bi ? f->uv : f->u, bi ? nullptr : f->v, f->pitch, bi ? f->pitch : f->pitch_uv,
+                          f->device ? TM_MEM_DEVICE : TM_MEM_HOST), "tm_mdsi_set_frame");
+            side = TM_SIDE_DIS;
+        }
+        ++filled;
+    }
+    void flush()
+    {
+        if (!filled) return;
+        chk(compute_async(x, filled), "tm_mdsi_compute_async");
+        chk(sync(x), "tm_mdsi_sync");
+        std::vector<tm_mdsi_frame> out(filled);
+        chk(get(x, 0, filled, out.data()), "tm_mdsi_get");
+        for (uint32_t i = 0; i < filled; ++i) {
+            const tm_mdsi_frame &f = out[i];
+            const double v = score(f.dev, f.n);
+            ready.push_back(v);
+            sum += v;
+            ++pairs;
+            if (map_prefix.empty()) continue;
+            const uint32_t wd = (w + f.factor - 1) / f.factor, hd = (h + f.factor - 1) / f.factor; // the library's own factor
+            map.resize((size_t)wd * hd);
+            chk(get_map(x, i, map.data(), (size_t)wd * sizeof(float)), "tm_mdsi_map");
+            char num[32];
+            snprintf(num, sizeof num, "%06zu.pfm", written++);
+            write_pfm_gray(map_prefix + num, wd, hd, map.data());
+        }
+        filled = 0;
+    }
+    double pop()
+    {
+        if (ready.empty()) throw std::logic_error("mdsi: a pair's result is missing");
+        const double v = ready.front();
+        ready.pop_front();
+        return v;
+    }
+    // MDSI does not pool across pictures: the mean of the pairs' values
+    double sequence_score() const { return pairs ? sum / (double)pairs : std::nan(""); }
+};
+
 // ---- CIEDE2000 ---------------------------------------------------------------------------------------------------------
 // libturbometrics_ciede.so, loaded at run time like the YUV library (a CLI run without -m ciede2000 never loads it).  Pairs are handed over
 // as -m psnr-yuv hands them over and computed batch by batch in stream order; a pair's two values (kCiedeNames: the score and the mean dE00)
@@ -1649,7 +1781,8 @@ TurboMetrics::TurboMetrics(uint32_t width, uint32_t height, const Metrics &metri
     if (metrics_.gmsd) gm_ = std::make_unique<GmsdRun>(w_, h_, batch_, metrics_.gmsd_population, metrics_.gmsd_map);
     if (metrics_.haarpsi) hp_ = std::make_unique<HaarpsiRun>(w_, h_, batch_, metrics_.haarpsi_map);
     if (metrics_.deitp) it_ = std::make_unique<ItpRun>(w_, h_, batch_, metrics_.itp_hlg, metrics_.itp_map);
-    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_ || hv_ || ci_ || si_ || gm_ || hp_ || it_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
+    if (metrics_.mdsi) md_ = std::make_unique<MdsiRun>(w_, h_, batch_, metrics_.mdsi_factor, metrics_.mdsi_map);
+    if (metrics_.mask() == 0 && (metrics_.xpsnr || metrics_.motion || metrics_.vif || metrics_.adm || metrics_.scenes || metrics_.cambi || metrics_.flip || yv_ || hv_ || ci_ || si_ || gm_ || hp_ || it_ || md_)) return; // -m xpsnr, -m vif, -m adm, --motion or --scenes alone: no SSIMULACRA2 / PSNR engine at all
     chk(tm_engine_create(&eng_[0], w_, h_, metrics_.mask(), batch_), "tm_engine_create");
     if (pipeline) {
         const int rc = tm_engine_create(&eng_[1], w_, h_, metrics_.mask(), batch_);
@@ -1962,6 +2095,8 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
     if (hp_) s_hp.emplace();
     std::optional<std::vector<double>> s_it[2]; // kItpNames
     if (it_) { s_it[0].emplace(); s_it[1].emplace(); }
+    std::optional<std::vector<double>> s_md;
+    if (md_) s_md.emplace();
     std::optional<FrameScores> held;
     auto emit = [&](const FrameScores &r) {
         if (on_frame) on_frame(r);
@@ -2055,6 +2190,10 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
                 const std::array<double, 2> v = it_->pop();
                 for (int k = 0; k < 2; ++k) { r.deitp[k] = v[k]; s_it[k]->push_back(v[k]); }
             }
+            if (md_) {
+                r.mdsi = md_->pop();
+                s_md->push_back(*r.mdsi);
+            }
             if (mo_) {
                 r.motion = mo_->pop();
                 if (held) {
@@ -2087,6 +2226,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (gm_) gm_->flush();
         if (hp_) hp_->flush();
         if (it_) it_->flush();
+        if (md_) md_->flush();
         in_flight[i] = true;
     };
 
@@ -2168,6 +2308,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
         if (gm_) gm_->push(fref, fdis);
         if (hp_) hp_->push(fref, fdis);
         if (it_) it_->push(fref, fdis, cref, cdis);
+        if (md_) md_->push(fref, fdis, cref, cdis);
         if (eng_[cur]) {
             set_frame(eng_[cur], filled[cur], TM_SIDE_REF, fref, cref);
             set_frame(eng_[cur], filled[cur], TM_SIDE_DIS, fdis, cdis);
@@ -2206,7 +2347,7 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
 
     MetricsResults res;
     res.frame_count = compute_count;
-    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_ || hv_ || ci_ || si_ || gm_ || hp_ || it_))
+    if (compute_count == 0 && (s_psnr || s_ssim || s_msssim || s_ssimu || xp_ || mo_ || vf_ || ad_ || sc_ || cb_ || fl_ || yv_ || hv_ || ci_ || si_ || gm_ || hp_ || it_ || md_))
         throw NoFramesSelected();
     if (xp_) {
         std::optional<MetricAggregate> *dst[3] = {&res.xpsnr_y, &res.xpsnr_u, &res.xpsnr_v};
@@ -2281,6 +2422,10 @@ MetricsResults TurboMetrics::compute_all(FrameSource &frames_ref, FrameSource &f
             res.deitp[k] = MetricAggregate::from(std::move(*s_it[k]));
             res.deitp[k]->sequence = it_->sequence_score(k);
         }
+    if (md_) {
+        res.mdsi = MetricAggregate::from(std::move(*s_md));
+        res.mdsi->sequence = md_->sequence_score();
+    }
     if (s_psnr) res.psnr = MetricAggregate::from(std::move(*s_psnr));
     if (s_ssim) res.ssim = MetricAggregate::from(std::move(*s_ssim));
     if (s_msssim) res.msssim = MetricAggregate::from(std::move(*s_msssim));

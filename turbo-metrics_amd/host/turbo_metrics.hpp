@@ -80,6 +80,11 @@ struct Metrics {
     // --itp-map (a prefix: every pair's dE ITP map as PREFIX%06d.pfm); not an engine metric
     bool deitp = false, itp_hlg = false;
     std::string itp_map;
+    // MDSI of 4:2:0 pairs (include/turbo_metrics_mdsi.h, libturbometrics_mdsi.so): the CLI's -m mdsi, --mdsi-factor (0: from the picture size) and
+    // --mdsi-map (a prefix: every pair's GCS map as PREFIX%06d.pfm); not an engine metric
+    bool mdsi = false;
+    uint32_t mdsi_factor = 0;
+    std::string mdsi_map;
     uint32_t mask() const
     {
         return (psnr ? (uint32_t)TM_METRIC_PSNR : 0u) | (ssim ? (uint32_t)TM_METRIC_SSIM : 0u) |
@@ -135,6 +140,8 @@ struct MetricsResults {
     std::optional<MetricAggregate> haarpsi;
     // -m deitp: [0] deitp (the pair's mean dE ITP), [1] deitp_max; sequence: the summed dE ITP over the summed positions, the largest maximum; names: kItpNames
     std::optional<MetricAggregate> deitp[2];
+    // -m mdsi; sequence: the mean of the pairs' values (MDSI does not pool across pictures)
+    std::optional<MetricAggregate> mdsi;
 };
 
 struct MetricsStats {
@@ -170,6 +177,7 @@ struct FrameScores {
     std::optional<double> gmsd[2]; // kGmsdNames
     std::optional<double> haarpsi;
     std::optional<double> deitp[2]; // kItpNames
+    std::optional<double> mdsi;
 };
 
 extern const char *const kYuvNames[8];
@@ -371,6 +379,7 @@ private:
     std::unique_ptr<struct YuvRun> yv_;                       // metrics_.psnr_yuv / ssim_yuv: the YUV PSNR / SSIM library's state (likewise; no history)
     std::unique_ptr<struct CiedeRun> ci_;                     // metrics_.ciede: the CIEDE2000 library's state (likewise; no history)
     std::unique_ptr<struct GmsdRun> gm_;                      // metrics_.gmsd: the GMSD library's state (likewise; no history)
+    std::unique_ptr<struct MdsiRun> md_;                      // metrics_.mdsi: the MDSI library's state (likewise; no history)
     std::unique_ptr<struct ItpRun> it_;                       // metrics_.deitp: the dE ITP library's state (likewise; no history)
     std::unique_ptr<struct HaarpsiRun> hp_;                   // metrics_.haarpsi: the HaarPSI library's state (likewise; no history)
     std::unique_ptr<struct HvsRun> hv_;                       // metrics_.psnr_hvs / psnr_hvs_m: the PSNR-HVS library's state (likewise; no history)
